@@ -21,7 +21,15 @@ timed region: the records of step k right after its kernels, its CIGAR bytes
 the GPU; all gathers are drained before the clock stops.  value = total cells
 of all ranks / max over ranks of the step time.
 
-Also reported (rank 0):
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, runs one untimed step
+and the W warmup steps, times the K steps and prints the result line with the
+headline figures (metric, value, unit, ms_per_step, dtype, config, plan).
+`--dump-outputs DIR` then writes what the last timed step computed -- per pair
+the score, target_begin, CIGAR length and CIGAR CRC32, plus the CIGAR bytes of
+a fixed seeded sample of pairs -- as DIR/<name>.npy; the inputs are seeded, so
+the same arguments give the same arrays from run to run and from build to build.
+
+Also reported with `--full` (rank 0), each from runs or checks of its own:
   roofline      -- the dominant fill kernel: algorithmic bytes per launch /
                    its HIP-event duration on its launch stream, against the
                    8 TB/s HBM peak; traffic = rocprofv3 PMC HBM bytes per launch
@@ -116,6 +124,14 @@ def parse(argv=None):
                     help="one batch after the other (no DevicePipeline overlap of a traceback with the next fill)")
     ap.add_argument("--flags", type=int, default=0, help="ta_plan_create TA_PLAN_* kernel-selection flags")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsal only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything listed under 'Also reported' "
+                         "(parity, serial steps, roofline / valu, host to host, score-only, gather check, CPU "
+                         "baseline; the --no-* options pick among them); without it a run sets up, warms up, "
+                         "times the steps and prints the headline figures only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the results of the last timed step (what a caller of the "
+                         "timed path receives) as DIR/<name>.npy, float64 / float32, at most 64 MB in all")
     a = ap.parse_args(argv)
     if a.workload == "cfg2":
         a.pairs = a.pairs or 10000
@@ -687,6 +703,39 @@ def load_profile(name, tag):
         return json.load(f).get(tag)
 
 
+DUMP_MAX_PAIRS = 250000  # per-pair arrays: every pair up to here, else a seeded sample of this many
+DUMP_CIGAR_BYTES = 8 * 2**20  # CIGAR bytes of a seeded sample of pairs (float32: 32 MB of the 64 MB allowed)
+
+
+def dump_outputs(dirname, per_pair, cigar_lens=None, cigar_of=None):
+    """--dump-outputs: DIR/<name>.npy (float64; the CIGAR bytes float32) of the
+    last timed step's results.  per_pair: {name: integer array [P]}; with CIGARs
+    also cigar_lens, cigar_crc32 and the bytes of a seeded sample of pairs
+    (cigar_sample_pairs, their CIGARs back to back in cigar_sample_bytes).
+    Every choice depends only on P and the results themselves."""
+    import zlib
+
+    os.makedirs(dirname, exist_ok=True)
+    P = len(next(iter(per_pair.values())))
+    rng = np.random.default_rng(0x5EED)
+    pairs = np.arange(P) if P <= DUMP_MAX_PAIRS else np.sort(rng.choice(P, DUMP_MAX_PAIRS, replace=False))
+    out = {"pairs": pairs.astype(np.float64)}
+    for name, a in per_pair.items():
+        out[name] = np.asarray(a)[pairs].astype(np.float64)
+    if cigar_lens is not None:
+        lens = np.asarray(cigar_lens)[pairs].astype(np.int64)
+        out["cigar_lens"] = lens.astype(np.float64)
+        out["cigar_crc32"] = np.array([zlib.crc32(cigar_of(int(p))) for p in pairs], np.float64)
+        order = rng.permutation(len(pairs))
+        take = np.sort(order[np.cumsum(lens[order]) <= DUMP_CIGAR_BYTES])
+        out["cigar_sample_pairs"] = pairs[take].astype(np.float64)
+        raw = b"".join(cigar_of(int(p)) for p in pairs[take])
+        out["cigar_sample_bytes"] = np.frombuffer(raw, np.uint8).astype(np.float32)
+    assert sum(a.nbytes for a in out.values()) <= 64 * 2**20
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 # --------------------------------------------------------------------------- workloads
 
 def main_align(args, D):
@@ -749,12 +798,13 @@ def main_align(args, D):
     # parity of this rank's own results (rank 0: the digest covers the first pairs of the stream),
     # from one step BEFORE the warmup: the checks take ~1 s of host time, and a GPU left idle that
     # long starts the next steps at a lower clock -- the warmup steps run right before the clock
+    # (a plain run keeps that one untimed step, so the timed steps see the same variants and slots)
     step()
     if gather:
         gather.drain()
     torch.cuda.synchronize(D.dev)
     parity = None
-    if D.rank == 0 and not args.no_parity:
+    if D.rank == 0 and args.full and not args.no_parity:
         res = plan.results()
         name, k = digest_name(args, plan.P)
         if name and cigar and not affine and lo == 0:
@@ -791,11 +841,24 @@ def main_align(args, D):
     gcups = cells_job / (ms / 1e3) / 1e9
 
     gathered = None
-    if gather and D.rank == 0:
+    if gather and D.rank == 0 and (args.full or args.dump_outputs):
         gathered = gather.last()
 
+    if args.dump_outputs and D.rank == 0:
+        # the last timed step's results as its caller holds them: every rank's gathered to rank 0,
+        # or this GPU's plan (config 2: in the order of the input variant that step aligned)
+        if gathered is not None:
+            sc_g, tb_g, cl_g, cig_g = gathered
+            offs = np.concatenate([[0], np.cumsum(cl_g.astype(np.int64))])
+            dump_outputs(args.dump_outputs, {"scores": sc_g, "target_begins": tb_g}, cl_g if cigar else None,
+                         lambda p: cig_g[offs[p]:offs[p + 1]])
+        else:
+            res = state["last"].results()
+            dump_outputs(args.dump_outputs, {"scores": res.scores, "target_begins": res.target_begins},
+                         res.cigar_lens, res.cigar)
+
     pipeline = None
-    if pipe and D.rank == 0:
+    if pipe and D.rank == 0 and args.full:
         # every slot's last batch (a different input variant per slot) against the reference
         # digest, read back through its rotation -- before the serial steps below reuse slot 0
         slots = []
@@ -832,7 +895,8 @@ def main_align(args, D):
                     "path": "align.DevicePipeline: one Aligner context (workspace) per slot; fills on a fill stream, "
                             "tracebacks on a walk stream, batch k's traceback beside batch k+1's fill"}
     out = None
-    if D.rank == 0:
+    detail = {}
+    if D.rank == 0 and args.full:
         # dominant kernel (fill) timed on its own launch stream with HIP events
         kt, tt = [], []
         for _ in range(max(min(args.steps, 10), 3)):
@@ -902,6 +966,13 @@ def main_align(args, D):
         if D.world == 1 and not args.no_cpu:
             cpu = cpu_baseline(host_batch_of(batch, dev_in, args.cpu_pairs), mode, sc, cigar,
                                args.cpu_pairs, args.cpu_pairs_1t, args.gap_open)
+        detail = {
+            "fill_ms": round(fill_ms, 4), "traceback_ms": round(float(np.mean(tt)), 4) if cigar else None,
+            "batch_latency_ms": round(fill_ms + (float(np.mean(tt)) if cigar else 0.0), 4),
+            "pipeline": pipeline,
+            "roofline": roof, "valu": valu, "cpu_baseline": cpu, "parity": parity, **extra,
+        }
+    if D.rank == 0:
         strong = args.workload == "cfg4"
         out = {
             "metric": METRIC, "value": round(gcups, 2), "unit": "GCUPS", "n_gpus": D.world, "steps": args.steps,
@@ -914,12 +985,9 @@ def main_align(args, D):
                        "parallelism": (f"one read set range-split by cells over {D.world} GPU(s)" if strong else
                                        f"pairs range-split over {D.world} GPU(s)")
                        + (", per-pair records and CIGAR bytes gathered to rank 0 every step (RCCL)" if D.world > 1 else "")},
-            "fill_ms": round(fill_ms, 4), "traceback_ms": round(float(np.mean(tt)), 4) if cigar else None,
-            "batch_latency_ms": round(fill_ms + (float(np.mean(tt)) if cigar else 0.0), 4),
             "chunks": plan.chunks, "workspace_gb": round(plan.workspace_bytes / 2**30, 2),
             "plan": {"dual_pairs": plan.dual_pairs, "flex_pairs": plan.flex_pairs, "fused_traceback": plan.fused},
-            "pipeline": pipeline,
-            "roofline": roof, "valu": valu, "cpu_baseline": cpu, "parity": parity, **extra,
+            "pipelined": pipe is not None, "full": args.full, **detail,
             "device": torch.cuda.get_device_name(D.dev),
         }
     if pipe:
@@ -1171,9 +1239,15 @@ def main_mapper(args, D):
     ms = elapsed / max(args.steps, 1) * 1e3
     out = None
     if D.rank == 0:
+        if args.dump_outputs:
+            per_pair = {k: getattr(r, k) for k in ("mapped", "strand_fwd", "q_begin", "q_end", "t_begin", "t_end", "scores")}
+            dump_outputs(args.dump_outputs, per_pair, r.cigar_len if opt.want_cigar else None, r.cigar)
         extra = {}
-        if D.world == 1 and not args.no_cpu:
-            extra = mapper_cpu_baseline_and_parity(g, rs, 24, args.mode, os.path.join(ROOT, "gpurun_out", "cfg3map"))
+        if D.world == 1 and args.full and not args.no_cpu:
+            import tempfile
+
+            with tempfile.TemporaryDirectory(prefix="cfg3map_") as tmp:
+                extra = mapper_cpu_baseline_and_parity(g, rs, 24, args.mode, tmp)
         out = {
             "metric": METRIC, "value": round(cells * D.world / (ms / 1e3) / 1e9, 2), "unit": "GCUPS",
             "n_gpus": D.world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),

@@ -7,13 +7,13 @@ set -u
 mkdir -p gpurun_out
 ok() { local rc=$1; [ "$rc" -eq 0 ] || [ "$rc" -eq 1 ]; }
 declare -A RUN=(
-  [cfg2]=""  # (bench.py defaults: the driver's own run)
-  [cfg3]="--workload cfg3 --steps 3 --warmup 1"
-  [cfg3_local]="--workload cfg3 --mode local --steps 3 --warmup 1"
-  [cfg3map]="--workload cfg3map --steps 2 --warmup 1"
-  [cfg4]="--workload cfg4 --steps 5 --warmup 1"
-  [cfg5_100k]="--workload cfg5 --pairs 100000 --steps 2 --warmup 1 --check-all"
-  [cfg5_100k_affine]="--workload cfg5 --pairs 100000 --gap-open -2 --steps 2 --warmup 1 --check-all"
+  [cfg2]="--full"  # (bench.py defaults, with every extra figure and check)
+  [cfg3]="--full --workload cfg3 --steps 3 --warmup 1"
+  [cfg3_local]="--full --workload cfg3 --mode local --steps 3 --warmup 1"
+  [cfg3map]="--full --workload cfg3map --steps 2 --warmup 1"
+  [cfg4]="--full --workload cfg4 --steps 5 --warmup 1"
+  [cfg5_100k]="--full --workload cfg5 --pairs 100000 --steps 2 --warmup 1 --check-all"
+  [cfg5_100k_affine]="--full --workload cfg5 --pairs 100000 --gap-open -2 --steps 2 --warmup 1 --check-all"
   [dropin]="--workload dropin"
 )
 ORDER=(cfg2 cfg3 cfg3_local cfg3map cfg4 cfg5_100k cfg5_100k_affine dropin)

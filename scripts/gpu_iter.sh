@@ -12,6 +12,7 @@ if [ -n "${PYTEST_K:-}" ]; then
   rc=$?; echo "pytest rc=$rc: $(tail -1 gpurun_out/pt_iter.log)"; [ $rc -eq 0 ] || exit 1
 fi
 IFS='|' read -ra SPECS <<< "${BENCH_SPECS:-}"
+SPECS=("${SPECS[@]/#/--full }")  # the figures printed below (fill, traceback, serial, parity) come with --full
 i=0
 for spec in "${SPECS[@]}"; do
   i=$((i + 1))

@@ -13,7 +13,7 @@ for grp in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES" \
            "SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_VMEM SQ_WAIT_ANY SQ_ACTIVE_INST_ANY"; do
   i=$((i + 1))
   timeout -s KILL 120 rocprofv3 --pmc $grp --output-format csv -d "$OUT/p$i" -o run \
-    -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu --no-parity --no-host --no-score-only "$@" > "$OUT/p$i.log" 2>&1
+    -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --full --no-cpu --no-parity --no-host --no-score-only "$@" > "$OUT/p$i.log" 2>&1
   echo "pass $i rc=$?"
 done
 python3 - "$OUT" <<'PY'

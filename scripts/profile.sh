@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 cd /tmp
 # --serial: one batch after the other, so that no two kernels' durations and
 # counters overlap (the pipelined steps run a walk beside the next fill)
-BARGS=(--steps 20 --warmup 3 --serial --no-cpu --no-parity --no-host --no-score-only "$@")
+BARGS=(--steps 20 --warmup 3 --serial --full --no-cpu --no-parity --no-host --no-score-only "$@")
 step() { # name timeout args...
   local name=$1 to=$2; shift 2
   echo "== $name" | tee -a "$OUT/profile.log"

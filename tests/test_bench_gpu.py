@@ -28,7 +28,7 @@ def _bench(*args, timeout=300):
 
 def test_cfg4_two_ranks_gathered_equals_one_gpu():
     out = _bench("--gpus", "2", "--workload", "cfg4", "--pairs", "300", "--dist-backend", "gloo", "--steps", "2",
-                 "--warmup", "1", "--no-cpu", "--workspace-gb", "8")
+                 "--warmup", "1", "--full", "--no-cpu", "--workspace-gb", "8")
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     g = out["gather"]
     assert g["bit_exact"] and g["pairs"] == 300 and g["digest"]["bit_exact"], g
@@ -37,7 +37,7 @@ def test_cfg4_two_ranks_gathered_equals_one_gpu():
 
 def test_cfg2_two_ranks_gather():
     out = _bench("--gpus", "2", "--pairs", "600", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
-                 "--no-cpu")
+                 "--full", "--no-cpu")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak"
     assert out["gather"]["bit_exact"] and out["gather"]["pairs_gathered"] == 1200, out["gather"]
 
@@ -55,7 +55,7 @@ def test_rccl_gather_world_one():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                         "--gpus", "1", "--dist-backend", "nccl", "--pairs", "600", "--steps", "2", "--warmup", "1",
-                        "--no-cpu", "--no-host", "--no-score-only"], env=env, capture_output=True, text=True,
+                        "--full", "--no-cpu", "--no-host", "--no-score-only"], env=env, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
