@@ -124,6 +124,9 @@ def lib() -> C.CDLL:
     L.ta_affine_plan_execute_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.ta_affine_plan_execute_traceback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.ta_affine_plan_check.argtypes = [C.c_void_p]
+    # the annotate post-pass (info records, =/X CIGARs)
+    L.ta_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ta_affine_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # the low-latency single-pair server (ta_server_*)
     L.ta_server_create.argtypes = [C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
     L.ta_server_destroy.argtypes = [C.c_void_p]
@@ -150,6 +153,7 @@ ABI_SYMBOLS = [
     "ta_affine_plan_execute_traceback", "ta_affine_plan_check", "ta_align_batch_affine",
     "ta_server_create", "ta_server_destroy", "ta_server_fits", "ta_server_align", "ta_server_running",
     "ta_server_last_times", "ta_server_pause", "ta_server_resume",
+    "ta_plan_annotate", "ta_affine_plan_annotate",
 ]
 # The drop-in C++ entry point (team_alignment.hpp), g++/libstdc++ cxx11 mangling.
 TEAM_ALIGN_SYMBOL = ("_ZN4team5AlignEPKcjS1_jNS_13AlignmentTypeEiiiPNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEEPj")
@@ -292,6 +296,26 @@ def align_affine(query: bytes, target: bytes, type, match: int, mismatch: int, g
     return int(res.scores[0]), res.cigar(0), int(res.target_begins[0])
 
 
+def align_annotated(query: bytes, target: bytes, type, match: int, mismatch: int, gap: int, gap_open=None):
+    """One pair through a DevicePlan with the annotate pass ->
+    (score, cigar bytes, target_begin, info dict, =/X cigar bytes).
+    gap_open=None: linear gaps; else the affine extension with gap_extend = gap."""
+    from .synth import from_pairs
+
+    _check_type(type)
+    plan = DevicePlan(default_aligner(), from_pairs([(bytes(query), bytes(target))]), type, match, mismatch, gap,
+                      want_cigar=True, gap_open=gap_open)
+    try:
+        plan.run()
+        plan.annotate(eqx=True)
+        res = plan.results()
+        ann = plan.annotation()
+    finally:
+        plan.close()
+    info = {f: int(ann.info[f][0]) for f in PAIR_INFO_DTYPE.names}
+    return int(res.scores[0]), res.cigar(0), int(res.target_begins[0]), info, ann.eqx(0)
+
+
 class Server:
     """The low-latency single-pair path (ta_server_*): a resident kernel, one
     wave per slot, serves one team::Align call at a time per slot -- what the
@@ -352,6 +376,37 @@ class _DeviceIO(C.Structure):
     _fields_ = [("query_bytes", C.c_void_p), ("query_off", C.c_void_p), ("target_bytes", C.c_void_p),
                 ("target_off", C.c_void_p), ("score", C.c_void_p), ("target_begin", C.c_void_p),
                 ("cigar_slots", C.c_void_p), ("cigar_start", C.c_void_p), ("cigar_len", C.c_void_p)]
+
+
+class PairInfo(C.Structure):
+    """ta_pair_info (include/team_align_c.h)."""
+
+    _fields_ = [(f, C.c_uint32) for f in ("query_begin", "query_end", "target_begin", "target_end", "n_eq", "n_x",
+                                          "n_ins", "n_del", "n_gap_runs", "n_free")]
+
+
+PAIR_INFO_DTYPE = np.dtype([(f, np.uint32) for f, _ in PairInfo._fields_])
+
+
+class _AnnotateIO(C.Structure):
+    _fields_ = [("info", C.c_void_p), ("eqx_slots", C.c_void_p), ("eqx_start", C.c_void_p), ("eqx_len", C.c_void_p)]
+
+
+@dataclass
+class Annotation:
+    """What DevicePlan.annotation() returns: ``info`` is a structured array
+    [P] with ta_pair_info's fields; ``eqx(p)`` the pair's =/X CIGAR bytes."""
+
+    info: np.ndarray
+    eqx_starts: np.ndarray | None
+    eqx_lens: np.ndarray | None
+    eqx_arena: np.ndarray | None
+
+    def eqx(self, p: int) -> bytes | None:
+        if self.eqx_arena is None:
+            return None
+        o = int(self.eqx_starts[p])
+        return self.eqx_arena[o : o + int(self.eqx_lens[p])].tobytes()
 
 
 def _results(o) -> BatchResult:
@@ -470,6 +525,36 @@ class DevicePlan:
         r = self._fn("ta_plan_check")(self._h)
         if r != TA_OK:
             _raise(r, self._ctx)
+
+    def annotate(self, eqx: bool = True):
+        """Enqueue the annotate pass (ta_plan_annotate) on the current stream,
+        after the run() it annotates: per-pair info records and, with ``eqx``,
+        the =/X CIGARs.  The tensors are allocated on first use."""
+        torch = self.torch
+        if getattr(self, "info", None) is None:
+            self.info = torch.zeros((self.P, 10), dtype=torch.int32, device=self.dev)
+        if eqx and getattr(self, "eqx_slots", None) is None:
+            self.eqx_slots = torch.zeros(max(self.slots_bytes, 1), dtype=torch.uint8, device=self.dev)
+            self.eqx_start = torch.zeros(self.P, dtype=torch.int64, device=self.dev)
+            self.eqx_len = torch.zeros(self.P, dtype=torch.int32, device=self.dev)
+        self._annotated_eqx = bool(eqx)
+        aio = _AnnotateIO(self.info.data_ptr(), self.eqx_slots.data_ptr() if eqx else None,
+                          self.eqx_start.data_ptr() if eqx else None, self.eqx_len.data_ptr() if eqx else None)
+        r = self._fn("ta_plan_annotate")(self._h, C.byref(self.io), C.byref(aio), self._stream())
+        if r != TA_OK:
+            _raise(r, self._ctx)
+
+    def annotation(self) -> Annotation:
+        """Synchronise, check and copy the last annotate()'s outputs to the host."""
+        if getattr(self, "info", None) is None:
+            raise RuntimeError("annotation(): no annotate() was enqueued")
+        self.check()
+        info = np.ascontiguousarray(self.info.cpu().numpy()).view(np.uint32).reshape(self.P, 10)
+        info = info.view(PAIR_INFO_DTYPE).reshape(self.P)
+        if not self._annotated_eqx:
+            return Annotation(info, None, None, None)
+        return Annotation(info, self.eqx_start.cpu().numpy().view(np.uint64),
+                          self.eqx_len.cpu().numpy().view(np.uint32), self.eqx_slots.cpu().numpy())
 
     def compact_cigars(self, out=None):
         """The CIGARs packed back to back on the device (ta_compact_cigars on

@@ -553,6 +553,23 @@ int ta_plan_check(ta_plan* pl) {
     return fail(pl->ctx, TA_ERR_DEVICE, plan_err_message(err));
 }
 
+int ta_plan_annotate(ta_plan* pl, const ta_device_io* io, const ta_annotate_io* out, void* stream) {
+    if (!pl || !io || !out) return TA_ERR_ARG;
+    ta_context* ctx = pl->ctx;
+    if (!pl->h.want_cigar) return fail(ctx, TA_ERR_ARG, "annotate: the plan has no CIGARs");
+    if (out->eqx_slots && (!out->eqx_start || !out->eqx_len)) return fail(ctx, TA_ERR_ARG, "annotate: eqx_slots without eqx_start / eqx_len");
+    if (int r = check_io(pl, io)) return r;
+    if (!pl->h.n_pairs) return TA_OK;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    ta::AnnotateArgs a{pl->h.n_pairs, pl->h.type, pl->d_qlen, pl->d_tlen, pl->d_goal_i, pl->d_goal_j, pl->d_slot_off,
+                       reinterpret_cast<const uint8_t*>(io->query_bytes), io->query_off,
+                       reinterpret_cast<const uint8_t*>(io->target_bytes), io->target_off, io->cigar_slots,
+                       io->cigar_start, io->cigar_len, out->info, out->eqx_slots, out->eqx_start, out->eqx_len};
+    TA_HIP(ctx, ta::launch_annotate(a, (hipStream_t)stream));
+    return TA_OK;
+}
+
 int ta_compact_cigars(ta_context* ctx, uint32_t n_pairs, const char* cigar_slots, const uint64_t* cigar_start,
                       const uint32_t* cigar_len, const uint64_t* dst_off, char* dst, void* stream) {
     if (!ctx) return TA_ERR_ARG;

@@ -121,6 +121,29 @@ struct CompactArgs {
     char* dst;
 };
 
+// The annotate post-pass (ta_annotate.hip): per-pair info records and extended
+// '=' / 'X' CIGARs from a finished execution's outputs and the plan's goal cells.
+struct AnnotateArgs {
+    uint32_t n_pairs;
+    int mode;
+    const uint32_t* qlen;
+    const uint32_t* tlen;
+    const uint32_t* goal_i;
+    const uint32_t* goal_j;
+    const uint64_t* slot_off;    // pair p's slot: [slot_off[p], + cigar_slot_bytes) in either arena
+    const uint8_t* qbytes;
+    const uint64_t* qoff;
+    const uint8_t* tbytes;
+    const uint64_t* toff;
+    const char* slots;           // the execution's CIGAR arena, starts and lengths
+    const uint64_t* cigar_start;
+    const uint32_t* cigar_len;
+    ta_pair_info* info;          // null: no records
+    char* eqx_slots;             // null: no extended CIGARs
+    uint64_t* eqx_start;
+    uint32_t* eqx_len;
+};
+
 // ---- the low-latency single-pair server (ta_server.cpp, serve_kernel in ta_kernels.hip)
 // A persistent kernel, one wave per slot, serves team::Align calls posted in
 // fine-grained pinned host memory: the host writes a request (lengths,
@@ -192,6 +215,8 @@ hipError_t launch_flex(int mode, bool cigar, const FillArgs& a, hipStream_t s);
 template <int MODE, bool CIGAR>
 hipError_t launch_flex_mode(const FillArgs& a, hipStream_t s);
 hipError_t launch_compact(const CompactArgs& a, hipStream_t s);
+// One wave per pair of the whole plan (ta_annotate.hip).
+hipError_t launch_annotate(const AnnotateArgs& a, hipStream_t s);
 // The server of one mode (slots waves, one per block): returns once launched.
 template <int MODE>
 hipError_t launch_serve_mode(const ServeArgs& a, uint32_t slots, hipStream_t s);

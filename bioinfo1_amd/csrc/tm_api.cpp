@@ -130,7 +130,7 @@ void tm_context_destroy(tm_context* c) {
     for (tmap::DevBuf* b : {&c->bytes, &c->off, &c->len, &m.entry_off, &m.tiles, &m.hash, &m.pos, &m.keep, &m.scan,
                           &m.kept_off, &m.khash, &m.kpos, &m.cub_tmp, &c->c_off, &c->c_f, &c->c_r, &c->c_out,
                           &c->c_prev, &c->c_lis, &c->m_qoff, &c->m_toff, &c->m_score, &c->m_tb, &c->m_slots,
-                          &c->m_cstart, &c->m_clen, &c->m_coff, &c->m_cdst, &c->match.cnt_f, &c->match.cnt_r, &c->match.off_f,
+                          &c->m_cstart, &c->m_clen, &c->m_coff, &c->m_cdst, &c->m_eslots, &c->m_estart, &c->m_elen, &c->m_info, &c->match.cnt_f, &c->match.cnt_r, &c->match.off_f,
                           &c->match.off_r, &c->match.key_f, &c->match.key_r, &c->match.hf, &c->match.hr,
                           &c->match.list_off, &c->match.cub_tmp})
         b->release();
@@ -225,7 +225,18 @@ int tm_map_batch(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const c
                  const uint32_t* len, const tm_options* opt, uint8_t* mapped, uint8_t* strand_fwd, uint32_t* q_begin,
                  uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end, int32_t* score, char* arena,
                  uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len) {
+    return tm_map_batch_x(ctx, idx, n_reads, bytes, off, len, opt, mapped, strand_fwd, q_begin, q_end, t_begin, t_end,
+                          score, arena, arena_bytes, cigar_off, cigar_len, 0, nullptr);
+}
+
+int tm_map_batch_x(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes, const uint64_t* off,
+                   const uint32_t* len, const tm_options* opt, uint8_t* mapped, uint8_t* strand_fwd, uint32_t* q_begin,
+                   uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end, int32_t* score, char* arena,
+                   uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags, ta_pair_info* info) {
     if (!ctx || !idx || !opt) return TM_ERR_ARG;
+    if (flags & ~TM_MAP_EQX) return fail(ctx, TM_ERR_ARG, "unknown flag");
+    if (info && !(flags & TM_MAP_EQX)) return fail(ctx, TM_ERR_ARG, "info needs TM_MAP_EQX");
+    const bool eqx = (flags & TM_MAP_EQX) != 0;
     if (opt->type != TA_GLOBAL && opt->type != TA_LOCAL && opt->type != TA_SEMI_GLOBAL)
         return fail(ctx, TM_ERR_BAD_TYPE, tm_status_string(TM_ERR_BAD_TYPE));
     if (opt->k != idx->k || opt->w != idx->w) return fail(ctx, TM_ERR_ARG, "k/w differ from the index");
@@ -289,6 +300,7 @@ int tm_map_batch(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const c
         strand_fwd[r] = fwd;
         score[r] = 0;
         if (opt->want_cigar) cigar_len[r] = 0;
+        if (info) info[r] = ta_pair_info{};
         if (!c[0]) {
             q_begin[r] = q_end[r] = t_begin[r] = t_end[r] = 0;
             continue;
@@ -316,7 +328,7 @@ int tm_map_batch(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const c
                                 ? ((uint64_t)free_b + ta_context_held_bytes(ctx->ta)) / 100 * 85
                                 : 0;
     int rc = ta_plan_create(ctx->ta, P, ql.data(), tl.data(), opt->type, opt->match, opt->mismatch, opt->gap,
-                            opt->want_cigar, budget, 0, &plan);
+                            opt->want_cigar || eqx, budget, 0, &plan);  // the annotate pass reads the CIGARs
     if (rc != TA_OK) return fail(ctx, rc == TA_ERR_BAD_TYPE ? TM_ERR_BAD_TYPE : TM_ERR_DEVICE,
                                  std::string("ta_plan_create: ") + ta_last_error(ctx->ta));
     const uint64_t slots = ta_plan_cigar_slots_bytes(plan);
@@ -345,14 +357,40 @@ int tm_map_batch(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const c
             return fail(ctx, TM_ERR_DEVICE, std::string("ta_plan_execute: ") + ta_last_error(ctx->ta) + " (" +
                                                 ta_status_string(r) + ")");
         if (int r = stage(5)) return r;
+        const char* c_slots = ctx->m_slots.as<const char>();
+        const uint64_t* c_start = ctx->m_cstart.as<const uint64_t>();
+        const uint32_t* c_len = ctx->m_clen.as<const uint32_t>();
+        std::vector<ta_pair_info> pinfo;
+        if (eqx) {  // info records and the =/X CIGARs, which take the base CIGARs' place below
+            TM_HIP(ctx, ctx->m_info.reserve(P * sizeof(ta_pair_info)));
+            ta_annotate_io ao{};
+            ao.info = ctx->m_info.as<ta_pair_info>();
+            if (opt->want_cigar) {
+                TM_HIP(ctx, ctx->m_eslots.reserve(slots + 1));
+                TM_HIP(ctx, ctx->m_estart.reserve(P * 8ull));
+                TM_HIP(ctx, ctx->m_elen.reserve(P * 4ull));
+                ao.eqx_slots = ctx->m_eslots.as<char>();
+                ao.eqx_start = ctx->m_estart.as<uint64_t>();
+                ao.eqx_len = ctx->m_elen.as<uint32_t>();
+                c_slots = ao.eqx_slots;
+                c_start = ao.eqx_start;
+                c_len = ao.eqx_len;
+            }
+            if (int r = ta_plan_annotate(plan, &io, &ao, s))
+                return fail(ctx, TM_ERR_DEVICE, std::string("ta_plan_annotate: ") + ta_last_error(ctx->ta) + " (" +
+                                                    ta_status_string(r) + ")");
+            if (info) {
+                pinfo.resize(P);
+                TM_HIP(ctx, hipMemcpyAsync(pinfo.data(), ctx->m_info.p, P * sizeof(ta_pair_info), hipMemcpyDeviceToHost, s));
+            }
+        }
         std::vector<int32_t> sc(P);
         TM_HIP(ctx, hipMemcpyAsync(sc.data(), ctx->m_score.p, P * 4ull, hipMemcpyDeviceToHost, s));
         std::vector<uint64_t> co;
         uint64_t total = 0;
         if (opt->want_cigar) {
             // pack the CIGAR slots on the device, then copy only the CIGAR bytes
-            if (int r = tmap::compact_segments(ctx, P, ctx->m_slots.as<const char>(), ctx->m_cstart.as<const uint64_t>(),
-                                               ctx->m_clen.as<const uint32_t>(), ctx->m_coff, ctx->m_cdst,
+            if (int r = tmap::compact_segments(ctx, P, c_slots, c_start, c_len, ctx->m_coff, ctx->m_cdst,
                                                ctx->match.cub_tmp, total))
                 return r;
             if (total > arena_bytes) return fail(ctx, TM_ERR_CAPACITY, "cigar arena too small");
@@ -367,6 +405,7 @@ int tm_map_batch(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const c
         for (uint32_t p = 0; p < P; ++p) {
             const uint32_t r = pair_read[p];
             score[r] = sc[p];
+            if (info) info[r] = pinfo[p];
             if (!opt->want_cigar) continue;
             cigar_off[r] = co[p];
             cigar_len[r] = (uint32_t)(co[p + 1] - co[p]);
@@ -401,7 +440,13 @@ int tm_align_plan_stats(const tm_context* ctx, uint64_t out[5]) {
 
 int tm_map_files(const char* reference_path, const char* reads_path, const tm_options* opt, const char* out_path,
                  int device) {
-    if (!reference_path || !reads_path || !opt || !out_path) return TM_ERR_ARG;
+    return tm_map_files_x(reference_path, reads_path, opt, out_path, device, 0);
+}
+
+int tm_map_files_x(const char* reference_path, const char* reads_path, const tm_options* opt, const char* out_path,
+                   int device, uint32_t flags) {
+    if (!reference_path || !reads_path || !opt || !out_path || (flags & ~TM_MAP_EQX)) return TM_ERR_ARG;
+    const bool eqx = (flags & TM_MAP_EQX) != 0;
     tmap::FastxFile ref, reads;
     std::string err;
     if (!tmap::read_fastx(reference_path, false, ref, err) || ref.records.empty()) {
@@ -454,9 +499,10 @@ int tm_map_files(const char* reference_path, const char* reads_path, const tm_op
         std::vector<int32_t> sc(nr);
         std::vector<uint64_t> co(nr);
         std::vector<char> arena(o.want_cigar ? arena_bytes : 0);
-        rc = tm_map_batch(ctx, idx, nr, reads.seq.data() + base, off.data(), len.data(), &o, mapped.data(), fwd.data(),
-                          qb.data(), qe.data(), tb.data(), te.data(), sc.data(), arena.data(), arena.size(), co.data(),
-                          cl.data());
+        std::vector<ta_pair_info> info(eqx ? nr : 0);
+        rc = tm_map_batch_x(ctx, idx, nr, reads.seq.data() + base, off.data(), len.data(), &o, mapped.data(),
+                            fwd.data(), qb.data(), qe.data(), tb.data(), te.data(), sc.data(), arena.data(), arena.size(),
+                            co.data(), cl.data(), flags, eqx ? info.data() : nullptr);
         if (rc) {
             std::fprintf(stderr, "map: %s: %s\n", tm_status_string(rc), tm_last_error(ctx));
             break;
@@ -477,6 +523,7 @@ int tm_map_files(const char* reference_path, const char* reads_path, const tm_op
                 line += "\tcg:Z:";
                 line.append(arena.data() + co[i], cl[i]);
             }
+            if (eqx) line += "\tNM:i:" + std::to_string((uint64_t)info[i].n_x + info[i].n_ins + info[i].n_del);
             line += '\n';
             std::fwrite(line.data(), 1, line.size(), out);
         }

@@ -91,6 +91,7 @@ struct tm_context {
     tmap::DevBuf c_off, c_f, c_r, c_out, c_prev, c_lis;
     // tm_map_batch
     tmap::DevBuf m_qoff, m_toff, m_score, m_tb, m_slots, m_cstart, m_clen, m_coff, m_cdst;
+    tmap::DevBuf m_eslots, m_estart, m_elen, m_info;  // TM_MAP_EQX: the annotate pass's outputs
     double stage_ms[tmap::kStages] = {};
     uint64_t stage_cells = 0;
     uint64_t plan_stats[5] = {};  // tm_align_plan_stats

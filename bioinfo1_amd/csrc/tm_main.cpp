@@ -36,6 +36,7 @@ int main(int argc, char** argv) {
     tm_options o{TA_GLOBAL, 1, -1, -1, 15, 5, 0.001, 0, 0};
     std::string f1, f2;
     int device = 0;
+    unsigned flags = 0;  // --eqx: =/X CIGARs and an NM tag (not in help(), which restates the reference's text)
     if (argc < 2) {
         std::fprintf(stderr, "Error: Not enough arguments\n");
         help();
@@ -74,6 +75,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(a, "-f") && more) o.f = std::strtod(argv[++i], nullptr);
         else if (!std::strcmp(a, "-d") && more) device = std::atoi(argv[++i]);
         else if (!std::strcmp(a, "-c")) o.want_cigar = 1;
+        else if (!std::strcmp(a, "--eqx")) flags |= TM_MAP_EQX;
         else if (!std::strcmp(a, "-s")) std::fprintf(stderr, "note: -s (statistics) is not part of this build\n");
         else if (f1.empty()) f1 = a;
         else if (f2.empty()) f2 = a;
@@ -88,7 +90,7 @@ int main(int argc, char** argv) {
         help();
         return 1;
     }
-    const int r = tm_map_files(f1.c_str(), f2.c_str(), &o, "-", device);
+    const int r = tm_map_files_x(f1.c_str(), f2.c_str(), &o, "-", device, flags);
     if (r != TM_OK && r != TM_ERR_INPUT) std::fprintf(stderr, "error: %s\n", tm_status_string(r));
     return r == TM_OK ? 0 : 1;
 }

@@ -31,7 +31,9 @@ TM_OK = 0
 # Every symbol include/team_mapper_c.h declares (checked by tests/test_abi.py).
 ABI_SYMBOLS = ["tm_status_string", "tm_last_error", "tm_context_create", "tm_context_destroy", "tm_minimizer_bound",
                "tm_minimize_batch", "tm_chain_batch", "tm_index_create", "tm_index_destroy", "tm_index_stats",
-               "tm_map_batch", "tm_stage_times", "tm_align_plan_stats", "tm_map_files"]
+               "tm_map_batch", "tm_stage_times", "tm_align_plan_stats", "tm_map_files", "tm_map_batch_x",
+               "tm_map_files_x"]
+TM_MAP_EQX = 1
 
 _lib = None
 
@@ -75,9 +77,11 @@ def lib() -> C.CDLL:
     L.tm_index_stats.argtypes = [vp, u64p, u64p, u64p, u64p, u32p, u32p]
     L.tm_map_batch.argtypes = [vp, vp, C.c_uint32, vp, u64p, u32p, C.POINTER(Options), u8p, u8p, u32p, u32p, u32p,
                                u32p, i32p, vp, C.c_uint64, u64p, u32p]
+    L.tm_map_batch_x.argtypes = L.tm_map_batch.argtypes + [C.c_uint32, vp]
     L.tm_stage_times.argtypes = [vp, C.POINTER(C.c_double), C.c_uint32, u64p]
     L.tm_align_plan_stats.argtypes = [vp, u64p]
     L.tm_map_files.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(Options), C.c_char_p, C.c_int]
+    L.tm_map_files_x.argtypes = L.tm_map_files.argtypes + [C.c_uint32]
     _lib = L
     return L
 
@@ -218,6 +222,7 @@ class MapResult:
     cigar_off: np.ndarray
     cigar_len: np.ndarray
     arena: np.ndarray
+    info: np.ndarray | None = None  # map_batch(eqx=True): ta_pair_info per read, window coordinates
 
     def cigar(self, r):
         o = int(self.cigar_off[r])
@@ -243,8 +248,9 @@ class Index:
         return dict(zip(["fwd_keys", "rev_keys", "fwd_positions", "rev_positions", "banned_fwd", "banned_rev"],
                         [x.value for x in v]))
 
-    def map_batch(self, reads, opt: Options) -> MapResult:
-        """reads: sequences, or a prepared (bytes, off, len) tuple (see soa())."""
+    def map_batch(self, reads, opt: Options, eqx: bool = False) -> MapResult:
+        """reads: sequences, or a prepared (bytes, off, len) tuple (see soa()).
+        eqx: tm_map_batch_x with TM_MAP_EQX -- =/X CIGARs and the info records."""
         L = lib()
         b, off, ln = _soa(reads)
         n = len(ln)
@@ -253,6 +259,16 @@ class Index:
                    scores=np.zeros(n, np.int32), cigar_off=np.zeros(n, np.uint64), cigar_len=np.zeros(n, np.uint32))
         cap = int((4 * ln.astype(np.uint64) + 2).sum()) if n else 0
         arena = np.zeros(max(cap, 1), np.uint8)
+        if eqx:
+            info = np.zeros(n, _align.PAIR_INFO_DTYPE)
+            _check(L.tm_map_batch_x(self.mapper._h, self._h, n, b.ctypes.data, _p(off, C.c_uint64),
+                                    _p(ln, C.c_uint32), C.byref(opt), _p(out["mapped"], C.c_uint8),
+                                    _p(out["strand_fwd"], C.c_uint8), _p(out["q_begin"], C.c_uint32),
+                                    _p(out["q_end"], C.c_uint32), _p(out["t_begin"], C.c_uint32),
+                                    _p(out["t_end"], C.c_uint32), _p(out["scores"], C.c_int32), arena.ctypes.data, cap,
+                                    _p(out["cigar_off"], C.c_uint64), _p(out["cigar_len"], C.c_uint32), TM_MAP_EQX,
+                                    info.ctypes.data), self.mapper._h)
+            return MapResult(arena=arena, info=info, **out)
         _check(L.tm_map_batch(self.mapper._h, self._h, n, b.ctypes.data, _p(off, C.c_uint64), _p(ln, C.c_uint32),
                               C.byref(opt), _p(out["mapped"], C.c_uint8), _p(out["strand_fwd"], C.c_uint8),
                               _p(out["q_begin"], C.c_uint32), _p(out["q_end"], C.c_uint32),

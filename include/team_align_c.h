@@ -249,6 +249,53 @@ int ta_compact_cigars(ta_context* ctx, uint32_t n_pairs, const char* cigar_slots
                       const uint32_t* cigar_len, const uint64_t* dst_off, char* dst, void* hip_stream);
 
 /*
+ * ---- Annotate: per-pair alignment coordinates, column counts and extended
+ * '=' / 'X' CIGARs, computed on the device from a finished execution.  The
+ * reference has no counterpart (team::Align returns a score, an M/I/D CIGAR
+ * and target_begin only).
+ *
+ * The alignment columns are the ops of the pair's CIGAR in order.  An M
+ * column at (i, j) is '=' when query[i] == target[j] as raw bytes
+ * (match_func, team_alignment.cpp:20-23) and 'X' otherwise.  The extended
+ * CIGAR is the same path with every M run split into maximal '=' / 'X' runs,
+ * in the same decimal run-length form ("1\0" for the empty op string); it
+ * never needs more than ta_cigar_slot_bytes(n, m) bytes, so its arena is
+ * ta_plan_cigar_slots_bytes() again, and pair p's text lies in the same byte
+ * range of that arena as its base CIGAR slot does in cigar_slots.
+ *
+ * The scored part of the path: global -- all of it; local -- all of it, ending
+ * at the goal cell (query_end, target_end = target_begin_out - 1), the begins
+ * being the ends minus the consumption; semi-global -- without the free first
+ * run (I along row 0 or D along column 0) and without the run appended after
+ * the goal cell (team_alignment.cpp:305-315): both are counted in n_free, the
+ * begins are the cell after the leading run and the ends the goal cell.
+ * Always n_eq + n_x + n_ins + n_del + n_free == the number of CIGAR columns.
+ */
+typedef struct ta_pair_info {
+    uint32_t query_begin, query_end;   /* scored part of the path, 0-based half-open */
+    uint32_t target_begin, target_end;
+    uint32_t n_eq, n_x, n_ins, n_del;  /* columns of each class inside the scored part */
+    uint32_t n_gap_runs;               /* maximal I runs + maximal D runs inside the scored part */
+    uint32_t n_free;                   /* columns outside it (semi-global free ends), else 0 */
+} ta_pair_info;                        /* 40 bytes */
+
+typedef struct ta_annotate_io {
+    ta_pair_info* info;    /* device, n_pairs; NULL = no records */
+    char* eqx_slots;       /* device, ta_plan_cigar_slots_bytes(), not the execution's cigar_slots; NULL = no extended CIGAR */
+    uint64_t* eqx_start;   /* device, n_pairs (with eqx_slots): pair p's text starts at eqx_slots[eqx_start[p]] */
+    uint32_t* eqx_len;     /* device, n_pairs (with eqx_slots) */
+} ta_annotate_io;
+
+/* Enqueue the annotate pass over all pairs (of all chunks) on hip_stream:
+ * asynchronous.  Enqueue it on the stream of the execution it annotates,
+ * after that execution and before the plan's next one: it reads the plan's
+ * goal cells and io's sequences, CIGAR slots, starts and lengths.
+ * ta_compact_cigars packs the extended CIGARs like the base ones.
+ * TA_ERR_ARG for a plan created with want_cigar == 0, a null io or out, and
+ * eqx_slots without eqx_start / eqx_len. */
+int ta_plan_annotate(ta_plan* plan, const ta_device_io* io, const ta_annotate_io* out, void* hip_stream);
+
+/*
  * ---- Affine-gap extension (BASELINE config 5: "affine gaps + full CIGAR
  * traceback").  The reference has NO counterpart: team::Align is linear-gap
  * only (team_alignment.cpp:25-28, 102-116; the "Gotoh" of
@@ -290,6 +337,9 @@ int ta_affine_plan_execute_traceback(ta_affine_plan* plan, const ta_device_io* i
 /* As ta_plan_check: TA_ERR_DEVICE when a pass hand-off poll of the packed
  * affine fill (one wave per couple and pass) gave up; clears the flag. */
 int ta_affine_plan_check(ta_affine_plan* plan);
+/* As ta_plan_annotate, for an affine plan's execution. */
+int ta_affine_plan_annotate(ta_affine_plan* plan, const ta_device_io* io, const ta_annotate_io* out,
+                            void* hip_stream);
 
 /* Host-memory batch with affine gaps: ta_align_batch with gap -> (gap_open, gap_extend). */
 int ta_align_batch_affine(ta_context* ctx, uint32_t n_pairs, const char* query_bytes, const uint64_t* query_off,

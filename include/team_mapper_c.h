@@ -28,6 +28,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "team_align_c.h" /* ta_pair_info */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -115,6 +117,20 @@ int tm_map_batch(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const c
                  uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end, int32_t* score, char* cigar_arena,
                  uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len);
 
+/* tm_map_batch with flags and the alignments' info records.  flags 0 and
+ * info NULL: tm_map_batch exactly.  TM_MAP_EQX: the CIGAR arena (when
+ * want_cigar) holds the extended '=' / 'X' CIGARs, and info (n_reads entries,
+ * when non-NULL; needs TM_MAP_EQX) gets each mapped read's ta_pair_info
+ * (team_align_c.h) in the coordinates of its two windows -- query_begin 0 is
+ * q_begin[r], target_begin 0 is t_begin[r] on the chain's strand; zeros for an
+ * unmapped read.  The records are computed with or without want_cigar. */
+#define TM_MAP_EQX 1u
+int tm_map_batch_x(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes, const uint64_t* off,
+                   const uint32_t* len, const tm_options* opt, uint8_t* mapped, uint8_t* strand_fwd, uint32_t* q_begin,
+                   uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end, int32_t* score, char* cigar_arena,
+                   uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags,
+                   ta_pair_info* info);
+
 /* Wall time (ms) of the last tm_map_batch on this context, per stage:
  * [0] read upload, [1] minimizers, [2] seed matching, [3] FindLIS chaining,
  * [4] windows + alignment plan (host), [5] alignment (fill + traceback),
@@ -134,6 +150,11 @@ int tm_align_plan_stats(const tm_context* ctx, uint64_t out[5]);
  */
 int tm_map_files(const char* reference_path, const char* reads_path, const tm_options* opt, const char* out_path,
                  int device);
+/* With TM_MAP_EQX (team_mapper_amd --eqx): cg:Z: carries the '=' / 'X' CIGAR
+ * and every line ends with "\tNM:i:<n_x + n_ins + n_del>" (with or without
+ * want_cigar).  flags 0: tm_map_files exactly. */
+int tm_map_files_x(const char* reference_path, const char* reads_path, const tm_options* opt, const char* out_path,
+                   int device, uint32_t flags);
 
 #ifdef __cplusplus
 }
