@@ -9,7 +9,9 @@
 //     planner's hmax for every cell, and every cell and candidate of the local
 //     flexible fill's frame (ta_layout.h flex_local_c0: zu - gap*r + H with the
 //     row-0 clamp base zu anywhere in its 65-step drift from c0) lies in
-//     [0, 0x7BFF].
+//     [0, 0x7BFF];
+//   * fits_int16 (global / semi and the local two-max frame, with the local argmax key)
+//     and flex_ck_fits over a wider scoring space and at their edges (below).
 // The DP is the reference's local recurrence (team_alignment.cpp:171-194) on
 // random bytes ('-' in targets, whose gap steps are free).  Prints "ok" or the
 // first violation; exit status 0 / 1.
@@ -150,6 +152,102 @@ int main(int argc, char** argv) {
                 if (mode == ta::kSemi && i == n && bad(h - (long)gap * n, "row n", i, j)) return 1;
             }
     }
+    // The same bounds over a wider scoring space and at their edges, every mode:
+    //   * fits_int16, global / semi: S = H - ma*j + gap*(j - i) of every cell and candidate,
+    //     of row 0 and column 0 (S(0, j) = (init + gap - ma) j, S(i, 0) = (init - gap) i), and the
+    //     semi row-n values H - gap*n, within int16;
+    //   * fits_int16, local (the two-max frame, off = dl = 0): S = 16H + z*j - i with
+    //     z = 1 - 16 ma of every cell, candidate and boundary within int16, and the argmax key
+    //     16H + 15 <= 32767 on the pair's own rows;
+    //   * flex_ck_fits where the planner asks it (flex_fits scorings): the checkpoints hold H as
+    //     int16 and the walk's window H plus at most (|gap| + |gap - ma|) * 48 (ta_walk_ck.hip).
+    // match, mismatch in [-10, 10], gap in [-8, 3]; every tenth case one magnitude in [64, 900];
+    // every tenth case within 2 % of the largest square the predicate admits; identical,
+    // disjoint and random inputs; rows n .. n + 15 hold byte 0, as the kernel's padding rows do.
+    long wide_cases = 0, wide_edge = 0, wide_ck = 0;
+    const int wide_iters = std::max(30, iters / 5);
+    for (int it = 0; it < wide_iters; ++it) {
+        const int mode = it % 3;
+        int sc[3] = {(int)(rng() % 21) - 10, (int)(rng() % 21) - 10, (int)(rng() % 12) - 8};
+        if (it % 10 == 5 || it % 30 == 0) {
+            const int v = 64 + (int)(rng() % 837), k = (int)(rng() % 3);
+            sc[k] = (k == 0 ? rng() % 4 != 0 : rng() % 4 == 0) ? v : -v;  // mostly match > 0 > mismatch, gap
+        }
+        const int ma = sc[0], mi = sc[1], gap = sc[2];
+        const bool flexs = ta::flex_fits(mode, ma, mi, gap);
+        uint32_t n = 1, m = 1;
+        bool near = false;
+        if (it % 10 == 0) {
+            // the largest admitted square, as tests/cpp/frame_probe.cpp's second mode finds it
+            // (every other time flex_ck_fits' edge, where the planner asks it)
+            const uint32_t cap = 11000;
+            const bool ck_edge = flexs && it % 20 == 10;
+            uint32_t L = cap;
+            while (L > 0 && !(ck_edge ? ta::flex_ck_fits(mode, L, L, ma, mi, gap) : ta::fits_int16(mode, L, L, ma, mi, gap)))
+                --L;
+            near = L > 0 && L < cap;
+            if (near) {
+                n = L - rng() % (L / 50 + 1);
+                m = L - rng() % (L / 50 + 1);
+                if (it % 20 == 0) n = m = L;
+            }
+        }
+        if (!near) {
+            const uint32_t big = (it % 10 == 1) ? 3000 : 90;
+            n = 1 + rng() % big;
+            m = 1 + rng() % big;
+        }
+        const bool fits = ta::fits_int16(mode, n, m, ma, mi, gap);
+        const bool ckf = flexs && ta::flex_ck_fits(mode, n, m, ma, mi, gap);
+        if (!fits && !ckf) continue;
+        ++wide_cases;
+        wide_edge += near;
+        wide_ck += ckf;
+        const int kind = (int)(rng() % 3), na = 2 + rng() % 4;
+        const char alpha[] = "ACGTN";
+        std::string q(n + 16, '\0'), t(m, 'C');
+        for (uint32_t i = 0; i < n; ++i) q[i] = kind == 1 ? 'A' : alpha[rng() % na];
+        for (uint32_t j = 0; j < m; ++j) t[j] = kind == 1 ? 'C' : kind == 0 ? (j < n ? q[j] : alpha[rng() % na]) : alpha[rng() % na];
+        const uint32_t N = n + 15;
+        const long init = mode == ta::kGlobal ? gap : 0;
+        const long z = 1 - 16L * ma;
+        const long slack = (std::labs(gap) + std::labs((long)gap - ma)) * 48;
+        auto bad = [&](long v, const char* what, uint32_t i, uint32_t j) {
+            ++checked;
+            if (v >= -32768 && v <= 32767) return false;
+            std::printf("%s violated: mode=%d n=%u m=%u sc=%d,%d,%d input=%d i=%u j=%u v=%ld\n", what, mode, n, m, ma, mi,
+                        gap, kind, i, j, v);
+            return true;
+        };
+        // the biased value of a cell value v at (i, j) in the dual fill's frame
+        auto S = [&](long v, long i, long j) {
+            return mode == ta::kLocal ? 16 * v + z * j - i : v - (long)ma * j + (long)gap * (j - i);
+        };
+        std::vector<long> Hp(m + 1), Hc(m + 1);
+        for (uint32_t j = 0; j <= m; ++j) {
+            Hp[j] = init * (long)j;
+            if (fits && bad(S(Hp[j], 0, j), "fits_int16 (row 0)", 0, j)) return 1;
+        }
+        for (uint32_t i = 1; i <= N; ++i) {
+            Hc[0] = init * (long)i;
+            if (fits && bad(S(Hc[0], i, 0), "fits_int16 (column 0)", i, 0)) return 1;
+            for (uint32_t j = 1; j <= m; ++j) {
+                const long d = Hp[j - 1] + (q[i - 1] == t[j - 1] ? ma : mi);
+                const long l = Hc[j - 1] + gap, u = Hp[j] + gap;
+                long h = std::max({d, l, u});
+                if (mode == ta::kLocal && h < 0) h = 0;
+                Hc[j] = h;
+                if (fits) {
+                    for (long cand : {d, l, u, h})
+                        if (bad(S(cand, i, j), "fits_int16 (cell)", i, j)) return 1;
+                    if (mode == ta::kSemi && i == n && bad(h - (long)gap * n, "fits_int16 (row n)", i, j)) return 1;
+                    if (mode == ta::kLocal && i <= n && bad(16 * h + 15, "fits_int16 (local key)", i, j)) return 1;
+                }
+                if (ckf && (bad(h + slack, "flex_ck_fits", i, j) || bad(h - slack, "flex_ck_fits", i, j))) return 1;
+            }
+            std::swap(Hp, Hc);
+        }
+    }
     // affine_fits_int16 (ta_planner.cpp) for the packed affine fill (ta_affine.hip):
     // S = V - ma*j + X*(j - i) for V = H, E, F and every candidate (diag, E open /
     // extend, F open / extend), the -inf stand-ins H - K, rows up to n + 15, the semi
@@ -211,6 +309,7 @@ int main(int argc, char** argv) {
         }
     }
     std::printf("ok: %ld values (%ld max3-offset cases, %ld flex-local cases, %ld global/semi dual cases, %ld affine "
-                "cases)\n", checked, dual_cases, flex_cases, lin_cases, aff_cases);
+                "cases, %ld wide-scoring cases: %ld at an edge, %ld with flex checkpoints)\n", checked, dual_cases,
+                flex_cases, lin_cases, aff_cases, wide_cases, wide_edge, wide_ck);
     return 0;
 }

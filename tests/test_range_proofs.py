@@ -3,7 +3,11 @@ patterns (ta_layout.h local_max3_offset, ta_planner.cpp flex_local_fits),
 checked by brute force on CPU: every biased value and candidate of the local
 DP (rows up to n + 15, '-' in targets, random scores including mismatch above
 match and positive gaps) lies in [0, 0x7BFF] whenever the bound admits the
-shape (tests/cpp/range_proofs.cpp)."""
+shape (tests/cpp/range_proofs.cpp).  Likewise fits_int16's global / semi frame,
+its local two-max frame with the argmax key 16 H + 15, and flex_ck_fits with
+the walk's window slack, over match and mismatch in [-10, 10], gap in [-8, 3]
+and magnitudes up to 900, with one case in ten at the predicate's edge and
+identical, disjoint and random inputs."""
 import os
 import subprocess
 
