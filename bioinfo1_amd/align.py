@@ -124,6 +124,26 @@ def lib() -> C.CDLL:
     L.ta_affine_plan_execute_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.ta_affine_plan_execute_traceback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.ta_affine_plan_check.argtypes = [C.c_void_p]
+    # banded extension (include/team_align_c.h, no reference counterpart)
+    L.ta_align_batch_banded.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64p, u32p, C.c_void_p, u64p, u32p, u32p,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, u32p, C.c_void_p,
+                                        C.c_uint64, u64p, u32p]
+    L.ta_banded_plan_create.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, u32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ta_banded_plan_destroy.argtypes = [C.c_void_p]
+    L.ta_banded_plan_destroy.restype = None
+    for f in ("ta_banded_plan_cigar_slots_bytes", "ta_banded_plan_workspace_bytes", "ta_banded_plan_band_cells",
+              "ta_banded_plan_swept_cells"):
+        getattr(L, f).restype = C.c_uint64
+        getattr(L, f).argtypes = [C.c_void_p]
+    L.ta_banded_plan_chunks.restype = C.c_uint32
+    L.ta_banded_plan_chunks.argtypes = [C.c_void_p]
+    L.ta_banded_plan_pair_chunks.argtypes = [C.c_void_p, u32p]
+    L.ta_banded_plan_execute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ta_banded_plan_execute_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ta_banded_plan_execute_traceback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ta_banded_plan_check.argtypes = [C.c_void_p]
+    L.ta_banded_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # the annotate post-pass (info records, =/X CIGARs)
     L.ta_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ta_affine_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -155,6 +175,15 @@ ABI_SYMBOLS = [
     "ta_server_last_times", "ta_server_pause", "ta_server_resume",
     "ta_plan_annotate", "ta_affine_plan_annotate",
 ]
+# The banded extension's symbols (checked by tests/test_banded_ref.py).
+BANDED_ABI_SYMBOLS = [
+    "ta_banded_plan_create", "ta_banded_plan_destroy", "ta_banded_plan_cigar_slots_bytes",
+    "ta_banded_plan_workspace_bytes", "ta_banded_plan_chunks", "ta_banded_plan_pair_chunks",
+    "ta_banded_plan_band_cells", "ta_banded_plan_swept_cells", "ta_banded_plan_execute",
+    "ta_banded_plan_execute_fill", "ta_banded_plan_execute_traceback", "ta_banded_plan_check",
+    "ta_banded_plan_annotate", "ta_align_batch_banded",
+]
+ABI_SYMBOLS += BANDED_ABI_SYMBOLS
 # The drop-in C++ entry point (team_alignment.hpp), g++/libstdc++ cxx11 mangling.
 TEAM_ALIGN_SYMBOL = ("_ZN4team5AlignEPKcjS1_jNS_13AlignmentTypeEiiiPNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEEPj")
 
@@ -177,6 +206,19 @@ def _raise(status: int, ctx=None):
 
 def _p(a, ct):
     return a.ctypes.data_as(C.POINTER(ct))
+
+
+def _band_array(band, n_pairs: int) -> np.ndarray:
+    """A band per pair as uint32 [P]: an int applies to every pair."""
+    if np.ndim(band) == 0:
+        b = np.full(n_pairs, int(band), np.int64)
+    else:
+        b = np.asarray(band, np.int64).reshape(-1)
+        if b.size != n_pairs:
+            raise ValueError(f"band: {b.size} entries for {n_pairs} pairs")
+    if b.size and (b.min() < 0 or b.max() > 0xFFFFFFFF):
+        raise ValueError("band: values must be in [0, 2^32)")
+    return np.ascontiguousarray(b.astype(np.uint32))
 
 
 @dataclass
@@ -239,7 +281,16 @@ class Aligner:
         exactly team::Align with gap = gap_extend."""
         return self._batch(batch, type, (match, mismatch, gap_open, gap_extend), want_cigar, affine=True)
 
-    def _batch(self, batch, type, scoring, want_cigar, affine) -> BatchResult:
+    def align_batch_banded(self, batch, type, match: int, mismatch: int, gap: int, band,
+                           want_cigar: bool = True) -> BatchResult:
+        """The banded extension (ta_align_batch_banded): only the cells with
+        min(0, m-n) - band <= j - i <= max(0, m-n) + band exist.  band: an int
+        or one per pair.  No reference counterpart; a band >= max(n, m) gives
+        exactly team::Align."""
+        return self._batch(batch, type, (match, mismatch, gap), want_cigar, affine=False,
+                           band=_band_array(band, batch.n_pairs))
+
+    def _batch(self, batch, type, scoring, want_cigar, affine, band=None) -> BatchResult:
         L = lib()
         t = _check_type(type)
         P = batch.n_pairs
@@ -255,9 +306,13 @@ class Aligner:
         qb = batch.qbytes if batch.qbytes.size else np.zeros(1, np.uint8)
         tbb = batch.tbytes if batch.tbytes.size else np.zeros(1, np.uint8)
         fn = L.ta_align_batch_affine if affine else L.ta_align_batch
+        extra = ()
+        if band is not None:
+            fn = L.ta_align_batch_banded
+            extra = (_p(band if band.size else np.zeros(1, np.uint32), C.c_uint32),)
         r = fn(
             self._h, P, qb.ctypes.data, _p(batch.qoff, C.c_uint64), _p(batch.qlen, C.c_uint32), tbb.ctypes.data,
-            _p(batch.toff, C.c_uint64), _p(batch.tlen, C.c_uint32), t, *scoring, int(bool(want_cigar)),
+            _p(batch.toff, C.c_uint64), _p(batch.tlen, C.c_uint32), *extra, t, *scoring, int(bool(want_cigar)),
             _p(sc, C.c_int32), _p(tb, C.c_uint32), arena.ctypes.data if want_cigar else None, cap,
             _p(coff, C.c_uint64) if want_cigar else None, _p(clen, C.c_uint32) if want_cigar else None)
         if r != TA_OK:
@@ -293,6 +348,17 @@ def align_affine(query: bytes, target: bytes, type, match: int, mismatch: int, g
     _check_type(type)
     res = default_aligner().align_batch_affine(from_pairs([(bytes(query), bytes(target))]), type, match, mismatch,
                                                gap_open, gap_extend, want_cigar)
+    return int(res.scores[0]), res.cigar(0), int(res.target_begins[0])
+
+
+def align_banded(query: bytes, target: bytes, type, match: int, mismatch: int, gap: int, band: int,
+                 want_cigar: bool = True):
+    """The banded extension for one pair -> (score, cigar bytes or None, target_begin)."""
+    from .synth import from_pairs
+
+    _check_type(type)
+    res = default_aligner().align_batch_banded(from_pairs([(bytes(query), bytes(target))]), type, match, mismatch,
+                                               gap, band, want_cigar)
     return int(res.scores[0]), res.cigar(0), int(res.target_begins[0])
 
 
@@ -429,16 +495,20 @@ class DevicePlan:
     current torch stream (asynchronous)."""
 
     def __init__(self, aligner: Aligner, batch, type, match, mismatch, gap, want_cigar=True, device=None,
-                 workspace_budget: int = 0, gap_open=None, flags: int = 0, inputs=None, records=None):
+                 workspace_budget: int = 0, gap_open=None, flags: int = 0, inputs=None, records=None, band=None):
         """gap_open=None: team::Align's linear gap.  gap_open=o: the affine-gap
         extension (ta_affine_plan_*) with gap_extend = gap.  flags: TA_PLAN_*
         kernel selection (tests / measurements; same results).  inputs: the
         batch already in HBM as (query bytes, query offsets, target bytes,
         target offsets) tensors -- then only batch.qlen / batch.tlen are read.
         records: an int32 device tensor of >= 3 * P entries that receives the
-        scores, target_begins and CIGAR lengths back to back (one download)."""
+        scores, target_begins and CIGAR lengths back to back (one download).
+        band=None: the whole matrix.  band=w (an int, or one per pair): the
+        banded extension (ta_banded_plan_*); not together with gap_open."""
         import torch
 
+        if band is not None and gap_open is not None:
+            raise ValueError("band and gap_open cannot be combined: the banded extension is linear-gap only")
         L = lib()
         t = _check_type(type)
         self.torch = torch
@@ -446,12 +516,17 @@ class DevicePlan:
         self.P = batch.n_pairs
         self.want_cigar = bool(want_cigar)
         self.affine = gap_open is not None
-        self._fn = (lambda name: getattr(L, name.replace("ta_plan_", "ta_affine_plan_"))) if self.affine else \
-            (lambda name: getattr(L, name))
+        self.banded = band is not None
+        family = "ta_affine_plan_" if self.affine else "ta_banded_plan_" if self.banded else "ta_plan_"
+        self._fn = lambda name: getattr(L, name.replace("ta_plan_", family))
         h = C.c_void_p()
         scoring = (match, mismatch, gap_open, gap) if self.affine else (match, mismatch, gap)
+        extra = ()
+        if self.banded:
+            self.band = _band_array(band, self.P)
+            extra = (_p(self.band if self.band.size else np.zeros(1, np.uint32), C.c_uint32),)
         r = self._fn("ta_plan_create")(aligner.handle, self.P, _p(batch.qlen, C.c_uint32),
-                                       _p(batch.tlen, C.c_uint32), t, *scoring, int(self.want_cigar),
+                                       _p(batch.tlen, C.c_uint32), *extra, t, *scoring, int(self.want_cigar),
                                        workspace_budget, flags, C.byref(h))
         if r != TA_OK:
             _raise(r, aligner.handle)
@@ -482,15 +557,31 @@ class DevicePlan:
                             self.slots.data_ptr(), self.cigar_start.data_ptr(), self.cigar_len.data_ptr())
         self.workspace_bytes = int(self._fn("ta_plan_workspace_bytes")(h))
         self.chunks = int(self._fn("ta_plan_chunks")(h))
-        self.dual_pairs = int(L.ta_affine_plan_dual_pairs(h)) if self.affine else int(L.ta_plan_dual_pairs(h))
-        self.flex_pairs = 0 if self.affine else int(L.ta_plan_flex_pairs(h))
-        self.fused = False if self.affine else bool(L.ta_plan_fused(h))
-        w = -1 if self.affine else int(L.ta_plan_walk(h))
+        linear = not (self.affine or self.banded)
+        self.dual_pairs = (int(L.ta_affine_plan_dual_pairs(h)) if self.affine else
+                           0 if self.banded else int(L.ta_plan_dual_pairs(h)))
+        self.flex_pairs = int(L.ta_plan_flex_pairs(h)) if linear else 0
+        self.fused = bool(L.ta_plan_fused(h)) if linear else False
+        w = int(L.ta_plan_walk(h)) if linear else -1
         self.walk, self.blk, self.ck = (w & 0xFF, bool(w & 0x100), bool(w & 0x200)) if w >= 0 else (None, False, False)
         self.aligner = aligner
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
+
+    @property
+    def band_cells(self) -> int:
+        """Banded plans: the in-band interior cells of all pairs (ta_banded_plan_band_cells)."""
+        if not self.banded:
+            raise AttributeError("band_cells: not a banded plan")
+        return int(lib().ta_banded_plan_band_cells(self._h))
+
+    @property
+    def swept_cells(self) -> int:
+        """Banded plans: the cells the kernels sweep (ta_banded_plan_swept_cells)."""
+        if not self.banded:
+            raise AttributeError("swept_cells: not a banded plan")
+        return int(lib().ta_banded_plan_swept_cells(self._h))
 
     def set_inputs(self, inputs):
         """Point the plan at another batch of the same shapes already in HBM:

@@ -1,0 +1,868 @@
+// bioinfo1_amd/csrc/ta_banded.hip -- the banded extension on gfx950: fill and
+// traceback kernels that compute only the cells within a per-pair band of
+// diagonals, and the ta_banded_plan host driver of include/team_align_c.h.
+//
+// The reference has no band; the semantics are DEFINED in
+// include/team_align_c.h (and restated in tests/banded_ref.py): team::Align's
+// recurrence, tie order, goals, walk and CIGAR format with the cells outside
+// lo <= j - i <= hi not existing.  A band that holds every cell gives
+// team::Align's results byte for byte.
+//
+// Layout.  The geometry of the linear int32 fill
+// (ta_kernels.hip run_pass): one wave64 per pair, lane l owns 16 query rows of
+// a 1024-row pass, one-step lane skew, DPP wave_shr:1 hand-off, the pass's
+// bottom row through a boundary row in HBM, raw-compare 2-bit codes in two bit
+// planes.  What the band changes:
+//   * pass p sweeps only the columns c0 .. c1 that hold an in-band cell of its
+//     rows (ta_layout.h band_c0 / band_c1); lane l is at column c0 + t - l at
+//     step t; the column left of c0 is column 0 (c0 == 1) or out of band;
+//   * inside that rectangle the cells off the band are forced to kSent after
+//     the local clamp and before the argmax, the goal scans and the boundary
+//     store.  |values| < 2^26 (the range rule), so a candidate formed from
+//     kSent = -2^27 is below every reachable value: it never wins, never ties;
+//   * the steps at which every lane's stripe lies wholly inside the band run
+//     the unmasked cell update (as run_pass keeps its ramps apart);
+//   * codes are stored for the swept steps only: per pass (c1 - c0 + 1 + 63)
+//     x 64 dwords, [step][lane], passes back to back (band_pass_offset).
+// The walk is traceback_pair's run-jumping walk (ta_device.h) over that
+// layout, with the shared RunWriter; local walks end at the STOP code.
+#include <hip/hip_runtime.h>
+#include <rocprofiler-sdk-roctx/roctx.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "../../include/team_align_c.h"
+#include "ta_context.h"
+#include "ta_device.h"
+#include "ta_host_batch.h"
+#include "ta_planner.h"
+
+namespace ta {
+namespace {
+
+constexpr int kSent = -(1 << 27);   // an out-of-band cell
+constexpr int kFloor = -(1 << 26);  // below every real value, above every value formed from kSent
+
+struct BandArgs {
+    const uint32_t* order;  // plan order; this launch handles order[begin .. begin+count)
+    uint32_t begin, count;
+    const uint8_t* qbytes;
+    const uint64_t* qoff;
+    const uint32_t* qlen;
+    const uint8_t* tbytes;
+    const uint64_t* toff;
+    const uint32_t* tlen;
+    const uint32_t* band;  // per pair, clamped (band_clamp)
+    int match, mismatch, gap;
+    uint32_t* ptrs;           // chunk workspace (2-bit codes)
+    const uint64_t* ptr_off;  // per pair, dwords from ptrs
+    int32_t* bnd;             // chunk pass-boundary rows
+    const uint64_t* bnd_off;  // per pair, words from bnd
+    int32_t* score;
+    uint32_t* target_begin;
+    uint32_t* goal_i;
+    uint32_t* goal_j;
+    char* slots;
+    const uint64_t* slot_off;
+    uint64_t* cigar_start;
+    uint32_t* cigar_len;
+};
+
+// One pass = rows row_base+1 .. row_base+nrows against the columns c0 .. c1.
+//   QDASH  some query row of this pass is '-' (its vertical gap steps are free)
+template <int MODE, bool CIGAR, bool QDASH>
+__device__ __forceinline__ PassOut band_pass(const BandArgs& a, const uint8_t* Q, const uint8_t* T, uint32_t n,
+                                             uint32_t m, uint32_t w, uint32_t pass, bool last_pass, uint32_t* prow,
+                                             int32_t* B, int lane) {
+    constexpr int R = kRows;
+    const int gap = a.gap, MA = a.match, MI = a.mismatch;
+    const int init = (MODE == kGlobal) ? gap : 0;  // :58-74
+    const int lo = band_lo(n, m, w), hi = band_hi(n, m, w);
+    const uint32_t BW = (uint32_t)(hi - lo);
+    const uint32_t row_base = pass * kPassRows;
+    const uint32_t nrows = min((uint32_t)kPassRows, n - row_base);
+    const uint32_t nl = (nrows + R - 1) / R;   // lanes in use
+    const uint32_t nv = nrows - (nl - 1) * R;  // valid rows of lane nl-1
+    const uint32_t vlim = (uint32_t)lane < nl - 1 ? R : ((uint32_t)lane == nl - 1 ? nv : 0u);
+    const bool has_next = !last_pass;
+    const uint32_t c0 = band_c0(n, m, w, pass), c1 = band_c1(n, m, w, pass);
+    const uint32_t ncols = c1 - c0 + 1;
+    const uint32_t steps = ncols + nl - 1;
+    const uint8_t* Tc = T + (c0 - 1);  // the byte of column c0 + k is Tc[k]
+    auto in_band = [&](int d) { return (uint32_t)(d - lo) <= BW; };
+
+    uint32_t qp[R / 4];  // the lane's 16 query bytes, 4 per register
+#pragma unroll
+    for (int k = 0; k < R / 4; ++k) {
+        uint32_t x = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const uint32_t i0 = row_base + (uint32_t)lane * R + 4 * k + b;
+            x |= (i0 < n ? (uint32_t)Q[i0] : 0u) << (8 * b);
+        }
+        qp[k] = x;
+    }
+    auto qbyte = [&](int r) { return (qp[r >> 2] >> (8 * (r & 3))) & 0xFFu; };
+    // column c0 - 1: the boundary column 0 where in band, else nothing
+    int H[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint32_t i = row_base + (uint32_t)lane * R + r + 1;
+        H[r] = (c0 == 1 && in_band(-(int)i)) ? wmul(i, init) : kSent;  // :83-86
+    }
+    const uint32_t i_above = row_base + (uint32_t)lane * R;  // the row above the stripe, at column c0 - 1
+    int recv = kSent;
+    if (in_band((int)(c0 - 1) - (int)i_above)) {
+        if (c0 == 1) recv = wmul(i_above, init);
+        else if (lane == 0) recv = B[c0 - 1];  // (c0 > 1 only below pass 0: the previous pass's bottom row)
+    }
+    int kc[R];  // local argmax key = 16 h + (15 - r) on valid rows
+    if constexpr (MODE == kLocal) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) kc[r] = (uint32_t)r < vlim ? (R - 1 - r) : -(1 << 30);
+    }
+    int tc = 0;
+    int bestkey = INT_MIN;
+    uint32_t bestj = 0;
+    int rowbest = kFloor;
+    uint32_t rowbest_j = 0;
+
+    // the previous pass's bottom row, 64 columns c0 + 64 k + lane per chunk; what it did
+    // not sweep (beyond its c1) is out of band in that row, and so is never read
+    auto load_top = [&](uint32_t k) {
+        const uint32_t j = c0 + k * 64u + (uint32_t)lane;
+        return (j <= m && in_band((int)j - (int)row_base)) ? B[j] : kSent;
+    };
+    uint32_t tcur = load_tchunk(Tc, ncols, 0, lane), tnext = load_tchunk(Tc, ncols, 1, lane);
+    int bcur = 0, bnext = 0;
+    if (pass > 0) {
+        bcur = load_top(0);
+        bnext = load_top(1);
+    }
+    // e - r = (j - i) - lo of the lane's row r at the coming step
+    int e = (int)c0 - (int)row_base - 1 - 17 * lane - lo;
+
+    auto step = [&](uint32_t t, auto masked_tag) {
+        constexpr bool MASKED = decltype(masked_tag)::value;
+        if ((t & 255u) == 0 && t) {
+            tcur = tnext;
+            tnext = load_tchunk(Tc, ncols, (t >> 8) + 1, lane);
+        }
+        int top;
+        if (pass == 0) {  // row 0, :89-92, where in band
+            top = (int)(c0 + t) <= hi ? wmul(c0 + t, init) : kSent;
+        } else {
+            if ((t & 63u) == 0 && t) {
+                bcur = bnext;
+                bnext = load_top((t >> 6) + 1);
+            }
+            top = rdlane(bcur, t & 63u);
+        }
+        const uint32_t word = (uint32_t)rdlane((int)tcur, (t >> 2) & 63u);
+        const int newc = (int)((word >> ((t & 3u) * 8)) & 0xFFu);
+        const int prev = recv;
+        recv = wave_shr1(top, H[R - 1]);
+        tc = wave_shr1(newc, tc);
+
+        const uint32_t jrel = t - (uint32_t)lane;  // column c0 + jrel
+        const bool active = !MASKED || (((uint32_t)lane < nl) & (jrel < ncols));
+        uint32_t accD = 0, accI = 0;
+        if (active) {
+            const int j = (int)(c0 + jrel);
+            const int gt = (tc == '-') ? 0 : gap;  // indel(t[j-1])
+            auto score_of = [&](int r) { return (qbyte(r) == (uint32_t)tc) ? MA : MI; };
+            int dnext = wadd(prev, score_of(0));
+            int upv = recv;
+            int stepkey = INT_MIN;
+            static_for<0, R>([&](auto rc) {
+                constexpr int r = decltype(rc)::value;
+                const int old = H[r];
+                const int diag = dnext;
+                const int left = wadd(old, gt);
+                if constexpr (r + 1 < R) dnext = wadd(old, score_of(r + 1));
+                int upg = gap;  // indel(q[i-1])
+                if (QDASH) upg = (qbyte(r) == (uint32_t)'-') ? 0 : gap;
+                const int up = wadd(upv, upg);
+                const int m1 = max(diag, left);
+                int h;
+                if (MODE == kLocal) h = max3_imm<0>(m1, up);  // clamp, :185
+                else h = max(m1, up);
+                if (CIGAR) {
+                    const uint64_t mD = ballot(up > m1);      // DELETE only if strictly greater
+                    const uint64_t mI = ballot(left > diag);  // INSERT beats MATCH only if strictly greater
+                    uint64_t dmask = mD, imask = mI;
+                    if (MODE == kLocal) {  // canonical codes: M=00 I=01 D=10 STOP=11
+                        const uint64_t mS = ballot(h == 0);  // cost 0 ends the walk (:202)
+                        dmask |= mS;
+                        imask = (mI & ~mD) | mS;
+                    }
+                    accD = shl1_add_lanebit(accD, dmask);
+                    accI = shl1_add_lanebit(accI, imask);
+                }
+                if (MASKED) h = ((uint32_t)(e - r) <= BW) ? h : kSent;  // off the band: no cell
+                if (MODE == kLocal) {  // (kSent << 4 would wrap: an out-of-band cell keys as h = -1)
+                    const int hk = MASKED ? max(h, -1) : h;
+                    stepkey = max(stepkey, (int)(((uint32_t)hk << 4) + (uint32_t)kc[r]));
+                }
+                H[r] = h;
+                upv = h;
+            });
+            if (MODE == kLocal) {
+                if (stepkey > bestkey) {  // strict: the first column keeps a tie (:186)
+                    bestkey = stepkey;
+                    bestj = (uint32_t)j;
+                }
+            }
+            if (MODE == kSemi && last_pass) {  // row n is register nv-1 of lane nl-1
+                const int rv = select_row<R>(H, nv - 1);
+                if (rv > rowbest) {
+                    rowbest = rv;
+                    rowbest_j = (uint32_t)j;
+                }
+            }
+            if (has_next && (uint32_t)lane == nl - 1) B[j] = H[R - 1];
+        }
+        if (CIGAR) prow[t * kWave + lane] = (accD << kDPlane) | accI;
+        ++e;
+    };
+    // Steps at which every lane in use is at a column of the pass and its whole
+    // stripe is in band: e - 15 >= 0 in lane nl-1 and e <= BW in lane 0.
+    const int e0 = (int)c0 - (int)row_base - 1 - lo;  // lane 0's e at step 0
+    const int t_in = max((int)nl - 1, 15 + 17 * ((int)nl - 1) - e0);
+    const int t_out = min((int)ncols, (int)BW - e0 + 1);  // first masked step after them
+    const uint32_t u0 = (uint32_t)min(max(t_in, 0), (int)steps);
+    const uint32_t u1 = (uint32_t)min(max(t_out, (int)u0), (int)steps);
+    uint32_t t = 0;
+    for (; t < u0; ++t) step(t, std::true_type{});
+    for (; t < u1; ++t) step(t, std::false_type{});
+    for (; t < steps; ++t) step(t, std::true_type{});
+
+    PassOut o{kFloor, 0, 0, kFloor, 0, 0};
+    if (MODE == kLocal) {
+        // h first over lanes (the row tag only orders rows inside a lane), then the first lane
+        const int hk = (uint32_t)lane < nl ? (bestkey >> 4) : INT_MIN;
+        const int mx = wave_max(hk);
+        const int fl = first_lane(hk == mx);
+        const int key = rdlane(bestkey, fl);
+        o.h = mx;
+        o.i = row_base + (uint32_t)fl * R + (uint32_t)(R - 1 - (key & 15)) + 1;
+        o.j = (uint32_t)rdlane((int)bestj, fl);
+    } else if (MODE == kSemi) {
+        if (c1 == m) {  // column m (H holds it now), i ascending, strict '>' (:265-270)
+            int cv = kFloor;
+            uint32_t cr = 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if ((uint32_t)r < vlim && H[r] > cv) {
+                    cv = H[r];
+                    cr = r;
+                }
+            const int mx = wave_max(cv);
+            if (mx > kFloor) {
+                const int fl = first_lane(cv == mx && vlim > 0);
+                o.h = mx;
+                o.i = row_base + (uint32_t)fl * R + (uint32_t)rdlane((int)cr, fl) + 1;
+                o.j = m;
+            }
+        }
+        if (last_pass) {
+            o.row_h = rdlane(rowbest, nl - 1);
+            o.row_j = (uint32_t)rdlane((int)rowbest_j, nl - 1);
+        }
+    } else {
+        if (last_pass) o.corner = rdlane(select_row<R>(H, nv - 1), nl - 1);  // H(n, m)
+    }
+    return o;
+}
+
+template <int MODE, bool CIGAR>
+__global__ __launch_bounds__(kBlock) void banded_fill_kernel(BandArgs a) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t widx = wave_id();
+    if (widx >= a.count) return;  // wave-uniform
+    const uint32_t p = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.order[a.begin + widx]);
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.qlen[p]);
+    const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.tlen[p]);
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.band[p]);
+    if (n == 0 || m == 0) {  // today's closed forms: the whole boundary is in band
+        if (lane == 0) {
+            int score = 0;
+            uint32_t gi = 0, gj = 0, tb = 0;
+            if (MODE == kGlobal) {
+                gi = n;
+                gj = m;
+                score = n ? wmul(n, a.gap) : wmul(m, a.gap);
+            } else if (MODE == kLocal) {
+                tb = 1;
+            } else {
+                gj = (n == 0) ? m : 0;
+            }
+            a.score[p] = score;
+            a.target_begin[p] = tb;
+            a.goal_i[p] = gi;
+            a.goal_j[p] = gj;
+        }
+        return;
+    }
+    const uint8_t* Q = a.qbytes + a.qoff[p];
+    const uint8_t* T = a.tbytes + a.toff[p];
+    const uint32_t passes = n_passes(n);
+    uint32_t* prow = CIGAR ? a.ptrs + a.ptr_off[p] : nullptr;
+    int32_t* B = (passes > 1) ? a.bnd + a.bnd_off[p] : nullptr;
+    const int lo = band_lo(n, m, w), hi = band_hi(n, m, w);
+
+    // semi: the column scan starts at (0, m) (cost 0) where that cell is in band
+    int best_h = (MODE == kSemi && (int)m <= hi) ? 0 : kFloor;
+    uint32_t best_i = 0, best_j = (MODE == kSemi) ? m : 0;
+    int corner = 0;
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+        const bool last_pass = pass + 1 == passes;
+        bool dash = false;
+        const uint32_t row0 = pass * kPassRows + (uint32_t)lane * kRows;
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) dash |= (row0 + r < n) && Q[row0 + r] == '-';
+        const PassOut o = __ballot(dash) ? band_pass<MODE, CIGAR, true>(a, Q, T, n, m, w, pass, last_pass, prow, B, lane)
+                                         : band_pass<MODE, CIGAR, false>(a, Q, T, n, m, w, pass, last_pass, prow, B, lane);
+        if (MODE != kGlobal && o.h > best_h) {  // strict: the upper pass wins ties
+            best_h = o.h;
+            best_i = o.i;
+            best_j = o.j;
+        }
+        if (MODE == kSemi && last_pass) {  // row n after column m (:271-278): (n, 0) first, cost 0
+            if (-(int)n >= lo && 0 > best_h) {
+                best_h = 0;
+                best_i = n;
+                best_j = 0;
+            }
+            if (o.row_h > best_h) {
+                best_h = o.row_h;
+                best_i = n;
+                best_j = o.row_j;
+            }
+        }
+        if (MODE == kGlobal && last_pass) corner = o.corner;
+        if (CIGAR) prow += (uint64_t)band_pass_steps(n, m, w, pass) * kWave;
+        if (!last_pass) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // boundary row -> next pass
+    }
+    if (lane == 0) {
+        a.score[p] = (MODE == kGlobal) ? corner : best_h;
+        a.target_begin[p] = (MODE == kLocal) ? best_j + 1 : 0;  // :117-121 / :197-199 / :283-285
+        a.goal_i[p] = (MODE == kGlobal) ? n : best_i;
+        a.goal_j[p] = (MODE == kGlobal) ? m : best_j;
+    }
+}
+
+// traceback_pair's walk (ta_device.h) over the banded code layout: the tile is
+// 64 steps x 4 stripes of the current pass, steps counted from the pass's c0.
+// Runs never leave the band: a candidate from an out-of-band cell never won,
+// so an I run ends at the band's lower edge, a D run at its upper edge, and an
+// M run stays on its diagonal.  Local walks end at the STOP code (cost 0).
+template <int MODE>
+__device__ __forceinline__ void band_traceback_pair(const uint32_t* P, uint32_t n, uint32_t m, uint32_t bw,
+                                                    uint32_t gi, uint32_t gj, char* slot, uint64_t cap, int lane,
+                                                    uint64_t* start_in_slot, uint32_t* len) {
+    RunWriter w{slot + cap, 0u, 0u, 0u, 0u, 0u, 0u, lane};
+    if (MODE == kSemi && (gj != m || gi != n)) {  // :306-315
+        if (gi == n) {
+            if (m - gj) w.push('I', m - gj);
+        } else if (gj == m && n - gi) {
+            w.push('D', n - gi);
+        }
+    }
+    uint32_t i = gi, j = gj;
+    uint32_t tP = 0xFFFFFFFFu, tt0 = 0, tL0 = 0, cur_ln = 0xFFFFFFFFu;
+    uint32_t pc0 = 0, psteps = 0;  // the pass's first column and stored steps
+    uint64_t pbase = 0;            // its first code dword
+    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, cur = 0;
+    while (true) {
+        if (MODE == kLocal) {
+            if (min(i, j) == 0) break;  // row / column 0: cost 0 (:202)
+        } else {
+            if (i == 0) {  // row 0: INSERT parents (:89-92)
+                if (j) w.push('I', j);
+                break;
+            }
+            if (j == 0) {  // column 0: DELETE parents (:83-86)
+                w.push('D', i);
+                break;
+            }
+        }
+        const uint32_t row = i - 1;
+        const uint32_t ln = (row >> 4) & 63u, r = row & 15u;
+        bool reload = false;
+        if ((row >> 10) != tP) {
+            tP = row >> 10;  // kPassRows = 1024
+            pc0 = band_c0(n, m, bw, tP);
+            psteps = band_pass_steps(n, m, bw, tP);
+            pbase = band_pass_offset(n, m, bw, tP);
+            reload = true;
+        }
+        const uint32_t t = (j - pc0) + ln;
+        if (reload || (int)((t - tt0) | (ln - tL0)) < 0) {
+            tL0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(max(ln, 3u) - 3u));
+            tt0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(max(t, 63u) - 63u));
+            const uint32_t ts = tt0 + (uint32_t)lane;
+            c0 = c1 = c2 = c3 = 0;
+            if (ts < psteps) {
+                const uint32_t* q = P + pbase + (uint64_t)ts * kWave + tL0;
+                c0 = q[0];
+                c1 = q[1];
+                c2 = q[2];
+                c3 = q[3];
+            }
+            cur_ln = 0xFFFFFFFFu;
+        }
+        if (ln != cur_ln) {
+            const uint32_t sel = ln - tL0;
+            cur = sel == 0 ? c0 : sel == 1 ? c1 : sel == 2 ? c2 : c3;
+            cur_ln = ln;
+        }
+        const uint32_t kk = t - tt0;
+        // x = dw >> (15 - r): bit 16 + k / bit k = D / I of row r - k
+        const uint32_t sh = 15u - r;
+        const uint32_t x = (uint32_t)rdlane((int)cur, kk) >> sh;
+        const uint32_t dflag = (x >> 16) & 1u, iflag = x & 1u;
+        if (MODE == kLocal && (dflag & iflag)) break;  // STOP: cost 0 (:202)
+        // D cells of rows r, r-1, ..: trailing ones (local: D and not STOP)
+        const uint32_t dp = (MODE == kLocal) ? ((x >> 16) & ~x) : (x >> 16);
+        const uint32_t drun = (uint32_t)__builtin_ctz(~dp);  // <= r + 1
+        // I: row r at every step; M: step tt0 + lane holds row r - (kk - lane)
+        const uint32_t lsh = sh + (kk - (uint32_t)lane) * (iflag ^ 1u);
+        const uint32_t v = (cur >> (lsh & 31u)) & 0x10001u;
+        const uint32_t streak = streak_down(ballot(v == iflag), kk);
+        const uint32_t hrun = min(streak, iflag ? j : min(j, r + 1u));
+        const uint32_t run = dflag ? drun : hrun;
+        const uint32_t op = dflag ? 'D' : ('M' - 4u * iflag);
+        w.push(op, run);
+        i -= (op == 'I') ? 0u : run;
+        j -= dflag ? 0u : run;
+    }
+    w.finish();
+    *start_in_slot = cap - w.used;
+    *len = w.used;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void banded_traceback_kernel(BandArgs a) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t widx = wave_id();
+    if (widx >= a.count) return;
+    const uint32_t p = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.order[a.begin + widx]);
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.qlen[p]);
+    const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.tlen[p]);
+    const uint32_t bw = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.band[p]);
+    const uint32_t gi = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.goal_i[p]);
+    const uint32_t gj = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.goal_j[p]);
+    uint64_t st;
+    uint32_t len;
+    band_traceback_pair<MODE>(a.ptrs + a.ptr_off[p], n, m, bw, gi, gj, a.slots + a.slot_off[p], cigar_slot_bytes(n, m),
+                              lane, &st, &len);
+    if (lane == 0) {
+        a.cigar_start[p] = a.slot_off[p] + st;
+        a.cigar_len[p] = len;
+    }
+}
+
+inline dim3 band_grid(uint32_t waves) { return dim3((waves + kWavesPerBlock - 1) / kWavesPerBlock); }
+
+hipError_t launch_banded_fill(int mode, bool cigar, const BandArgs& a, hipStream_t s) {
+    if (a.count == 0) return hipSuccess;
+    const dim3 g = band_grid(a.count), b(kBlock);
+#define TA_BAND_FILL(M)                                                                 \
+    case M:                                                                             \
+        if (cigar) hipLaunchKernelGGL((banded_fill_kernel<M, true>), g, b, 0, s, a);    \
+        else hipLaunchKernelGGL((banded_fill_kernel<M, false>), g, b, 0, s, a);         \
+        break;
+    switch (mode) {
+        TA_BAND_FILL(kGlobal)
+        TA_BAND_FILL(kLocal)
+        TA_BAND_FILL(kSemi)
+        default: return hipErrorInvalidValue;
+    }
+#undef TA_BAND_FILL
+    return hipGetLastError();
+}
+
+hipError_t launch_banded_traceback(int mode, const BandArgs& a, hipStream_t s) {
+    if (a.count == 0) return hipSuccess;
+    const dim3 g = band_grid(a.count), b(kBlock);
+    switch (mode) {
+        case kGlobal: hipLaunchKernelGGL(banded_traceback_kernel<kGlobal>, g, b, 0, s, a); break;
+        case kLocal: hipLaunchKernelGGL(banded_traceback_kernel<kLocal>, g, b, 0, s, a); break;
+        case kSemi: hipLaunchKernelGGL(banded_traceback_kernel<kSemi>, g, b, 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The plan: pairs by descending swept cells (the long ones start first), chunks
+// closed when the next pair's codes would pass the budget.
+struct BandPlan {
+    uint32_t n_pairs = 0;
+    int type = 0, match = 0, mismatch = 0, gap = 0;
+    bool want_cigar = false;
+    std::vector<uint32_t> qlen, tlen, band, order;
+    std::vector<uint64_t> ptr_off, bnd_off, slot_off;
+    struct Chunk {
+        uint32_t begin, count;
+        uint64_t ptr_dwords, bnd_words;
+    };
+    std::vector<Chunk> chunks;
+    uint64_t slots_bytes = 0, ws_ptr_dwords = 0, ws_bnd_words = 0;
+    uint64_t band_cells = 0, swept_cells = 0;
+};
+
+void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
+                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget) {
+    pl = BandPlan{};
+    pl.n_pairs = n_pairs;
+    pl.type = type;
+    pl.match = match;
+    pl.mismatch = mismatch;
+    pl.gap = gap;
+    pl.want_cigar = want_cigar;
+    pl.qlen.assign(qlen, qlen + n_pairs);
+    pl.tlen.assign(tlen, tlen + n_pairs);
+    pl.band.resize(n_pairs);
+    std::vector<uint64_t> swept(n_pairs);
+    pl.slot_off.resize(n_pairs);
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+        pl.band[p] = band_clamp(qlen[p], tlen[p], band[p]);
+        swept[p] = band_swept_cells(qlen[p], tlen[p], pl.band[p]);
+        pl.swept_cells += swept[p];
+        pl.band_cells += band_cells(qlen[p], tlen[p], pl.band[p]);
+        pl.slot_off[p] = pl.slots_bytes;
+        pl.slots_bytes += cigar_slot_bytes(qlen[p], tlen[p]);
+    }
+    pl.order.resize(n_pairs);
+    std::iota(pl.order.begin(), pl.order.end(), 0u);
+    std::stable_sort(pl.order.begin(), pl.order.end(), [&](uint32_t x, uint32_t y) { return swept[x] > swept[y]; });
+    const uint64_t budget_dw = std::max<uint64_t>(budget / 4, 1);
+    pl.ptr_off.assign(n_pairs, 0);
+    pl.bnd_off.assign(n_pairs, 0);
+    BandPlan::Chunk c{0, 0, 0, 0};
+    for (uint32_t k = 0; k < n_pairs; ++k) {
+        const uint32_t p = pl.order[k];
+        const uint64_t codes = want_cigar ? band_ptr_dwords(qlen[p], tlen[p], pl.band[p]) : 0;
+        if (c.count && c.ptr_dwords + codes > budget_dw) {
+            pl.chunks.push_back(c);
+            c = {k, 0, 0, 0};
+        }
+        pl.ptr_off[p] = c.ptr_dwords;
+        pl.bnd_off[p] = c.bnd_words;
+        c.ptr_dwords += codes;
+        c.bnd_words += bnd_words(qlen[p], tlen[p]);
+        ++c.count;
+    }
+    if (c.count) pl.chunks.push_back(c);
+    for (const auto& ch : pl.chunks) {
+        pl.ws_ptr_dwords = std::max(pl.ws_ptr_dwords, ch.ptr_dwords);
+        pl.ws_bnd_words = std::max(pl.ws_bnd_words, ch.bnd_words);
+    }
+}
+
+}  // namespace
+}  // namespace ta
+
+// ---------------------------------------------------------------------------
+// Host driver.
+struct ta_banded_plan {
+    ta_context* ctx = nullptr;
+    ta::BandPlan h;
+    void* own_block = nullptr;  // device arrays of a plan made by ta_banded_plan_create (one allocation)
+    uint32_t *d_qlen = nullptr, *d_tlen = nullptr, *d_band = nullptr, *d_order = nullptr;
+    uint32_t *d_goal_i = nullptr, *d_goal_j = nullptr;
+    uint64_t *d_ptr_off = nullptr, *d_bnd_off = nullptr, *d_slot_off = nullptr;
+};
+
+namespace {
+
+using ta_host::fail;
+
+struct BandOffs {
+    uint64_t qlen, tlen, band, order, ptr_off, bnd_off, slot_off;  // uploaded
+    uint64_t goal_i, goal_j;                                       // device-only
+};
+
+template <class T>
+uint64_t bvbytes(const std::vector<T>& v) {
+    return v.size() * sizeof(T);
+}
+
+BandOffs band_layout(const ta::BandPlan& h, ta::BlockLayout& L) {
+    BandOffs o{};
+    o.qlen = L.add(bvbytes(h.qlen));
+    o.tlen = L.add(bvbytes(h.tlen));
+    o.band = L.add(bvbytes(h.band));
+    o.order = L.add(bvbytes(h.order));
+    o.ptr_off = L.add(bvbytes(h.ptr_off));
+    o.bnd_off = L.add(bvbytes(h.bnd_off));
+    o.slot_off = L.add(bvbytes(h.slot_off));
+    return o;
+}
+
+void band_layout_scratch(const ta::BandPlan& h, ta::BlockLayout& L, BandOffs& o) {
+    o.goal_i = L.add(4ull * h.n_pairs);
+    o.goal_j = L.add(4ull * h.n_pairs);
+}
+
+void band_pack(const ta::BandPlan& h, const BandOffs& o, uint8_t* base) {
+    auto put = [&](uint64_t at, const auto& v) {
+        if (!v.empty()) std::memcpy(base + at, v.data(), bvbytes(v));
+    };
+    put(o.qlen, h.qlen);
+    put(o.tlen, h.tlen);
+    put(o.band, h.band);
+    put(o.order, h.order);
+    put(o.ptr_off, h.ptr_off);
+    put(o.bnd_off, h.bnd_off);
+    put(o.slot_off, h.slot_off);
+}
+
+void band_bind(ta_banded_plan* pl, uint8_t* d, const BandOffs& o) {
+    auto u32 = [&](uint64_t at) { return reinterpret_cast<uint32_t*>(d + at); };
+    auto u64 = [&](uint64_t at) { return reinterpret_cast<uint64_t*>(d + at); };
+    pl->d_qlen = u32(o.qlen);
+    pl->d_tlen = u32(o.tlen);
+    pl->d_band = u32(o.band);
+    pl->d_order = u32(o.order);
+    pl->d_ptr_off = u64(o.ptr_off);
+    pl->d_bnd_off = u64(o.bnd_off);
+    pl->d_slot_off = u64(o.slot_off);
+    pl->d_goal_i = u32(o.goal_i);
+    pl->d_goal_j = u32(o.goal_j);
+}
+
+// the range rule of include/team_align_c.h: every |value| < 2^26
+bool band_in_range(uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, int match, int mismatch, int gap) {
+    uint64_t maxn = 0, maxm = 0;
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+        maxn = std::max<uint64_t>(maxn, qlen[p]);
+        maxm = std::max<uint64_t>(maxm, tlen[p]);
+    }
+    const long long pm = std::max({std::llabs(match), std::llabs(mismatch), std::llabs(gap)});
+    return (long long)(maxn + maxm + 2) * pm < (1ll << 26);
+}
+
+int band_check_args(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
+                    const uint32_t* band, int type, int match, int mismatch, int gap) {
+    if (!ctx) return TA_ERR_ARG;
+    if (n_pairs && (!qlen || !tlen || !band)) return fail(ctx, TA_ERR_ARG, "null argument");
+    if (type != TA_GLOBAL && type != TA_LOCAL && type != TA_SEMI_GLOBAL)
+        return fail(ctx, TA_ERR_BAD_TYPE, ta_status_string(TA_ERR_BAD_TYPE));
+    if (!band_in_range(n_pairs, qlen, tlen, match, mismatch, gap))
+        return fail(ctx, TA_ERR_RANGE, ta_status_string(TA_ERR_RANGE));
+    return TA_OK;
+}
+
+int band_check_io(ta_banded_plan* pl, const ta_device_io* io) {
+    if (!pl || !io) return TA_ERR_ARG;
+    if (pl->h.n_pairs && (!io->query_off || !io->target_off || !io->score || !io->target_begin))
+        return fail(pl->ctx, TA_ERR_ARG, "null device pointer");
+    if (pl->h.want_cigar && pl->h.n_pairs && (!io->cigar_slots || !io->cigar_start || !io->cigar_len))
+        return fail(pl->ctx, TA_ERR_ARG, "null cigar device pointer");
+    return TA_OK;
+}
+
+int band_exec_chunk(ta_banded_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace) {
+    ta_context* ctx = pl->ctx;
+    const ta::BandPlan& h = pl->h;
+    if (int r = ta_host::grow(ctx, ctx->ws_ptrs, h.ws_ptr_dwords * 4)) return r;
+    if (int r = ta_host::grow(ctx, ctx->ws_bnd, h.ws_bnd_words * 4)) return r;
+    const auto& ch = h.chunks[c];
+    ta::BandArgs a{};
+    a.order = pl->d_order;
+    a.begin = ch.begin;
+    a.count = ch.count;
+    a.qbytes = (const uint8_t*)io->query_bytes;
+    a.qoff = io->query_off;
+    a.qlen = pl->d_qlen;
+    a.tbytes = (const uint8_t*)io->target_bytes;
+    a.toff = io->target_off;
+    a.tlen = pl->d_tlen;
+    a.band = pl->d_band;
+    a.match = h.match;
+    a.mismatch = h.mismatch;
+    a.gap = h.gap;
+    a.ptrs = (uint32_t*)ctx->ws_ptrs.p;
+    a.ptr_off = pl->d_ptr_off;
+    a.bnd = (int32_t*)ctx->ws_bnd.p;
+    a.bnd_off = pl->d_bnd_off;
+    a.score = io->score;
+    a.target_begin = io->target_begin;
+    a.goal_i = pl->d_goal_i;
+    a.goal_j = pl->d_goal_j;
+    a.slots = io->cigar_slots;
+    a.slot_off = pl->d_slot_off;
+    a.cigar_start = io->cigar_start;
+    a.cigar_len = io->cigar_len;
+    if (fill) {
+        roctxRangePushA("ta banded fill");
+        TA_HIP(ctx, ta::launch_banded_fill(h.type, h.want_cigar, a, s));
+        roctxRangePop();
+    }
+    if (trace && h.want_cigar) {
+        roctxRangePushA("ta banded traceback");
+        TA_HIP(ctx, ta::launch_banded_traceback(h.type, a, s));
+        roctxRangePop();
+    }
+    return TA_OK;
+}
+
+int band_exec(ta_banded_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t chunk, bool fill, bool trace) {
+    ta_context* ctx = pl->ctx;
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    if (int r = ta_host::stream_enter(ctx, s)) return r;
+    const uint32_t c0 = chunk == UINT32_MAX ? 0 : chunk;
+    const uint32_t c1 = chunk == UINT32_MAX ? (uint32_t)pl->h.chunks.size() : chunk + 1;
+    for (uint32_t c = c0; c < c1; ++c)
+        if (int r = band_exec_chunk(pl, io, s, c, fill, trace)) return r;
+    return ta_host::stream_leave(ctx, s);
+}
+
+struct BandHostPlan final : ta_host::HostPlan {
+    ta_banded_plan* pl;
+    BandOffs o{};
+    explicit BandHostPlan(ta_banded_plan* p) : pl(p) {}
+    void layout(ta::BlockLayout& L) override { o = band_layout(pl->h, L); }
+    void pack(uint8_t* base) override { band_pack(pl->h, o, base); }
+    void layout_device_only(ta::BlockLayout& L) override { band_layout_scratch(pl->h, L, o); }
+    void bind(uint8_t* dev) override { band_bind(pl, dev, o); }
+    int execute(const ta_device_io* io, hipStream_t s) override { return band_exec(pl, io, s, UINT32_MAX, true, true); }
+    uint64_t slots_bytes() const override { return pl->h.slots_bytes; }
+    uint64_t err_offset() const override { return UINT64_MAX; }  // (no polls: one wave sweeps a pair's passes)
+    const char* err_message(uint32_t) const override { return ""; }
+};
+
+}  // namespace
+
+extern "C" {
+
+void ta_banded_plan_destroy(ta_banded_plan* pl) {
+    if (!pl) return;
+    if (pl->own_block) {
+        (void)hipSetDevice(pl->ctx->device);
+        (void)hipFree(pl->own_block);
+    }
+    delete pl;
+}
+
+int ta_banded_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
+                          const uint32_t* band, int type, int match, int mismatch, int gap, int want_cigar,
+                          uint64_t budget, uint32_t flags, ta_banded_plan** out) {
+    (void)flags;
+    if (!out) return TA_ERR_ARG;
+    *out = nullptr;
+    if (int r = band_check_args(ctx, n_pairs, qlen, tlen, band, type, match, mismatch, gap)) return r;
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    auto* pl = new ta_banded_plan();
+    pl->ctx = ctx;
+    ta::build_band_plan(pl->h, n_pairs, qlen, tlen, band, type, match, mismatch, gap, want_cigar != 0,
+                        budget ? budget : ta_host::default_budget(ctx));
+    ta::BlockLayout L;
+    BandOffs o = band_layout(pl->h, L);
+    const uint64_t upload = L.bytes;
+    band_layout_scratch(pl->h, L, o);
+    std::vector<uint8_t> host(upload);
+    band_pack(pl->h, o, host.data());
+    hipError_t e = hipMalloc(&pl->own_block, std::max<uint64_t>(L.bytes, 256));
+    if (e == hipSuccess && upload) e = hipMemcpy(pl->own_block, host.data(), upload, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        ta_banded_plan_destroy(pl);
+        return fail(ctx, TA_ERR_DEVICE, std::string("ta_banded_plan_create: ") + hipGetErrorString(e));
+    }
+    band_bind(pl, static_cast<uint8_t*>(pl->own_block), o);
+    *out = pl;
+    return TA_OK;
+}
+
+uint64_t ta_banded_plan_cigar_slots_bytes(const ta_banded_plan* pl) { return pl ? pl->h.slots_bytes : 0; }
+uint64_t ta_banded_plan_workspace_bytes(const ta_banded_plan* pl) {
+    return pl ? pl->h.ws_ptr_dwords * 4 + pl->h.ws_bnd_words * 4 : 0;
+}
+uint32_t ta_banded_plan_chunks(const ta_banded_plan* pl) { return pl ? (uint32_t)pl->h.chunks.size() : 0; }
+uint64_t ta_banded_plan_band_cells(const ta_banded_plan* pl) { return pl ? pl->h.band_cells : 0; }
+uint64_t ta_banded_plan_swept_cells(const ta_banded_plan* pl) { return pl ? pl->h.swept_cells : 0; }
+
+int ta_banded_plan_pair_chunks(const ta_banded_plan* pl, uint32_t* chunk_of_pair) {
+    if (!pl || !chunk_of_pair) return TA_ERR_ARG;
+    for (uint32_t c = 0; c < (uint32_t)pl->h.chunks.size(); ++c) {
+        const auto& ch = pl->h.chunks[c];
+        for (uint32_t k = ch.begin; k < ch.begin + ch.count; ++k) chunk_of_pair[pl->h.order[k]] = c;
+    }
+    return TA_OK;
+}
+
+int ta_banded_plan_check(ta_banded_plan* pl) { return pl ? TA_OK : TA_ERR_ARG; }
+
+int ta_banded_plan_execute(ta_banded_plan* pl, const ta_device_io* io, void* stream) {
+    if (int r = band_check_io(pl, io)) return r;
+    std::lock_guard<std::mutex> lock(pl->ctx->mu);
+    return band_exec(pl, io, (hipStream_t)stream, UINT32_MAX, true, true);
+}
+
+int ta_banded_plan_execute_fill(ta_banded_plan* pl, const ta_device_io* io, void* stream, uint32_t chunk) {
+    if (int r = band_check_io(pl, io)) return r;
+    if (chunk >= pl->h.chunks.size()) return pl->h.n_pairs ? TA_ERR_ARG : TA_OK;
+    std::lock_guard<std::mutex> lock(pl->ctx->mu);
+    return band_exec(pl, io, (hipStream_t)stream, chunk, true, false);
+}
+
+int ta_banded_plan_execute_traceback(ta_banded_plan* pl, const ta_device_io* io, void* stream, uint32_t chunk) {
+    if (int r = band_check_io(pl, io)) return r;
+    if (chunk >= pl->h.chunks.size()) return pl->h.n_pairs ? TA_ERR_ARG : TA_OK;
+    std::lock_guard<std::mutex> lock(pl->ctx->mu);
+    return band_exec(pl, io, (hipStream_t)stream, chunk, false, true);
+}
+
+int ta_banded_plan_annotate(ta_banded_plan* pl, const ta_device_io* io, const ta_annotate_io* out, void* stream) {
+    if (!pl || !io || !out) return TA_ERR_ARG;
+    ta_context* ctx = pl->ctx;
+    if (!pl->h.want_cigar) return fail(ctx, TA_ERR_ARG, "annotate: the plan has no CIGARs");
+    if (out->eqx_slots && (!out->eqx_start || !out->eqx_len))
+        return fail(ctx, TA_ERR_ARG, "annotate: eqx_slots without eqx_start / eqx_len");
+    if (int r = band_check_io(pl, io)) return r;
+    if (!pl->h.n_pairs) return TA_OK;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    ta::AnnotateArgs a{pl->h.n_pairs, pl->h.type, pl->d_qlen, pl->d_tlen, pl->d_goal_i, pl->d_goal_j, pl->d_slot_off,
+                       reinterpret_cast<const uint8_t*>(io->query_bytes), io->query_off,
+                       reinterpret_cast<const uint8_t*>(io->target_bytes), io->target_off, io->cigar_slots,
+                       io->cigar_start, io->cigar_len, out->info, out->eqx_slots, out->eqx_start, out->eqx_len};
+    TA_HIP(ctx, ta::launch_annotate(a, (hipStream_t)stream));
+    return TA_OK;
+}
+
+int ta_align_batch_banded(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
+                          const uint32_t* qlen, const char* tbytes, const uint64_t* toff, const uint32_t* tlen,
+                          const uint32_t* band, int type, int match, int mismatch, int gap, int want_cigar,
+                          int32_t* score, uint32_t* target_begin, char* arena, uint64_t arena_bytes,
+                          uint64_t* cigar_off, uint32_t* cigar_len) {
+    uint64_t qend = 0, tend = 0;
+    if (int r = ta_host::check_host_batch(ctx, type, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, want_cigar, arena,
+                                          cigar_off, cigar_len, &qend, &tend))
+        return r;
+    if (n_pairs == 0) return TA_OK;
+    if (int r = band_check_args(ctx, n_pairs, qlen, tlen, band, type, match, mismatch, gap)) return r;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    ta_banded_plan pl;
+    pl.ctx = ctx;
+    uint64_t need = 0;
+    if (want_cigar)
+        for (uint32_t p = 0; p < n_pairs; ++p) need += 4 * ta::band_ptr_dwords(qlen[p], tlen[p], band[p]);
+    // everything in one chunk while the codes take at most 1 GiB (no device query per call)
+    const uint64_t budget = need <= (1ull << 30) ? std::max<uint64_t>(need, 1) : ta_host::default_budget(ctx);
+    ta::build_band_plan(pl.h, n_pairs, qlen, tlen, band, type, match, mismatch, gap, want_cigar != 0, budget);
+    BandHostPlan hp(&pl);
+    return ta_host::host_batch(ctx, hp, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
+                               target_begin, arena, arena_bytes, cigar_off, cigar_len);
+}
+
+}  // extern "C"

@@ -124,6 +124,71 @@ TA_HD inline int ck_decode(int s, int off, int zstep, int dl, int i, int j, int 
 TA_HD inline uint64_t bnd_words(uint32_t n, uint32_t m) {
     return n_passes(n) > 1 ? (uint64_t)m + 1 + kWave : 0;
 }
+// ---- Banded extension (ta_banded.hip; the definition is in
+// include/team_align_c.h).  Cell (i, j) is in band iff lo <= j - i <= hi with
+// lo = min(0, m - n) - w and hi = max(0, m - n) + w; a band of w >= max(n, m)
+// holds every cell, so w is clamped there and every figure fits an int32.
+TA_HD inline uint32_t band_clamp(uint32_t n, uint32_t m, uint32_t w) {
+    const uint32_t full = n > m ? n : m;
+    return w < full ? w : full;
+}
+TA_HD inline int band_lo(uint32_t n, uint32_t m, uint32_t w) {
+    const int d = (int)m - (int)n;
+    return (d < 0 ? d : 0) - (int)band_clamp(n, m, w);
+}
+TA_HD inline int band_hi(uint32_t n, uint32_t m, uint32_t w) {
+    const int d = (int)m - (int)n;
+    return (d > 0 ? d : 0) + (int)band_clamp(n, m, w);
+}
+// Pass p (rows 1024 p + 1 ..) sweeps the columns c0 .. c1 that hold an in-band
+// cell of one of its rows; c0 <= c1 always, because every row has one.
+TA_HD inline uint32_t band_c0(uint32_t n, uint32_t m, uint32_t w, uint32_t pass) {
+    const int c = (int)(pass * kPassRows) + 1 + band_lo(n, m, w);
+    return c > 1 ? (uint32_t)c : 1u;
+}
+TA_HD inline uint32_t band_c1(uint32_t n, uint32_t m, uint32_t w, uint32_t pass) {
+    const uint32_t row_base = pass * kPassRows;
+    const uint32_t nrows = n - row_base < (uint32_t)kPassRows ? n - row_base : (uint32_t)kPassRows;
+    const uint32_t c = row_base + nrows + (uint32_t)band_hi(n, m, w);
+    return c < m ? c : m;
+}
+// Steps whose codes pass p stores: its columns plus the lane skew.
+TA_HD inline uint32_t band_pass_steps(uint32_t n, uint32_t m, uint32_t w, uint32_t pass) {
+    return band_c1(n, m, w, pass) - band_c0(n, m, w, pass) + 1 + (kWave - 1);
+}
+// First code dword of pass p in the pair's region ([step][lane] within a pass).
+TA_HD inline uint64_t band_pass_offset(uint32_t n, uint32_t m, uint32_t w, uint32_t pass) {
+    uint64_t steps = 0;
+    for (uint32_t p = 0; p < pass; ++p) steps += band_pass_steps(n, m, w, p);
+    return steps * kWave;
+}
+TA_HD inline uint64_t band_ptr_dwords(uint32_t n, uint32_t m, uint32_t w) {
+    return (n == 0 || m == 0) ? 0 : band_pass_offset(n, m, w, n_passes(n));
+}
+// In-band interior cells (1 <= i <= n, 1 <= j <= m) and the cells the passes sweep.
+TA_HD inline uint64_t band_cells(uint32_t n, uint32_t m, uint32_t w) {
+    if (n == 0 || m == 0) return 0;
+    const long long lo = band_lo(n, m, w), hi = band_hi(n, m, w);
+    const long long N = n, M = m;
+    // row i holds columns max(1, i + lo) .. min(m, i + hi): sum both ends over i = 1 .. n
+    long long k1 = M - hi;  // rows i <= k1 end at i + hi, the others at m
+    k1 = k1 < 0 ? 0 : (k1 > N ? N : k1);
+    const long long ends = k1 * (k1 + 1) / 2 + k1 * hi + (N - k1) * M;
+    long long k2 = -lo;  // rows i <= k2 begin at column 1, the others at i + lo
+    k2 = k2 > N ? N : k2;
+    const long long begins = k2 + (N * (N + 1) / 2 - k2 * (k2 + 1) / 2) + (N - k2) * lo;
+    return (uint64_t)(ends - begins + N);
+}
+TA_HD inline uint64_t band_swept_cells(uint32_t n, uint32_t m, uint32_t w) {
+    if (n == 0 || m == 0) return 0;
+    uint64_t cells = 0;
+    for (uint32_t p = 0; p < n_passes(n); ++p) {
+        const uint32_t nrows = n - p * kPassRows < (uint32_t)kPassRows ? n - p * kPassRows : (uint32_t)kPassRows;
+        cells += (uint64_t)(band_c1(n, m, w, p) - band_c0(n, m, w, p) + 1) * nrows;
+    }
+    return cells;
+}
+
 // Upper bound on any run-length CIGAR of an n x m pair (team_alignment.cpp:145-160).
 TA_HD inline uint64_t cigar_slot_bytes(uint32_t n, uint32_t m) {
     return 2ull * ((uint64_t)n + m) + 2;

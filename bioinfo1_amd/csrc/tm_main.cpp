@@ -37,6 +37,8 @@ int main(int argc, char** argv) {
     std::string f1, f2;
     int device = 0;
     unsigned flags = 0;  // --eqx: =/X CIGARs and an NM tag (not in help(), which restates the reference's text)
+    bool banded = false;  // --band N: every window through the banded extension (not in help() either)
+    unsigned band = 0;
     if (argc < 2) {
         std::fprintf(stderr, "Error: Not enough arguments\n");
         help();
@@ -76,6 +78,16 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(a, "-d") && more) device = std::atoi(argv[++i]);
         else if (!std::strcmp(a, "-c")) o.want_cigar = 1;
         else if (!std::strcmp(a, "--eqx")) flags |= TM_MAP_EQX;
+        else if (!std::strcmp(a, "--band") && more) {
+            char* end = nullptr;
+            const unsigned long long v = std::strtoull(argv[++i], &end, 10);
+            if (end == argv[i] || *end || argv[i][0] == '-' || v > 0xFFFFFFFFull) {
+                std::fprintf(stderr, "Error: --band expects a number in [0, 2^32)\n");
+                return 1;
+            }
+            banded = true;
+            band = (unsigned)v;
+        }
         else if (!std::strcmp(a, "-s")) std::fprintf(stderr, "note: -s (statistics) is not part of this build\n");
         else if (f1.empty()) f1 = a;
         else if (f2.empty()) f2 = a;
@@ -90,7 +102,8 @@ int main(int argc, char** argv) {
         help();
         return 1;
     }
-    const int r = tm_map_files_x(f1.c_str(), f2.c_str(), &o, "-", device, flags);
+    const int r = banded ? tm_map_files_band(f1.c_str(), f2.c_str(), &o, "-", device, flags, band)
+                         : tm_map_files_x(f1.c_str(), f2.c_str(), &o, "-", device, flags);
     if (r != TM_OK && r != TM_ERR_INPUT) std::fprintf(stderr, "error: %s\n", tm_status_string(r));
     return r == TM_OK ? 0 : 1;
 }

@@ -348,6 +348,71 @@ int ta_align_batch_affine(ta_context* ctx, uint32_t n_pairs, const char* query_b
                           int gap_extend, int want_cigar, int32_t* score, uint32_t* target_begin,
                           char* cigar_arena, uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len);
 
+/*
+ * ---- Banded extension: only the cells within a per-pair band of diagonals
+ * are computed, so work and code workspace grow with n * band instead of
+ * n * m.  The reference has NO counterpart (team::Align fills the whole
+ * matrix); like the affine extension this is a plan family of its own and
+ * nothing above changes behaviour.
+ *
+ * Definition, for a pair of lengths n (query) and m (target) and its band w:
+ *   The band.  Cell (i, j), 0 <= i <= n, 0 <= j <= m, is in band iff
+ *     lo <= j - i <= hi,  lo = min(0, m - n) - w,  hi = max(0, m - n) + w.
+ *   (0, 0) and (n, m) are always in band; w >= max(n, m) puts every cell in
+ *   band; boundary cells (row 0, column 0) obey the same rule.
+ *   The recurrence is team::Align's (oracle/align_oracle.c restates it) with
+ *   out-of-band cells not existing: for an in-band interior cell MATCH is
+ *   always a candidate (its predecessor lies on the same diagonal), INSERT
+ *   (left) and DELETE (up) only when their predecessor cell is in band.  Tie
+ *   order (strict '>', M, then I, then D), free gap steps at '-' bytes, the
+ *   local clamp and its "parent kept" rule are unchanged.
+ *   Goals.  Global: (n, m).  Local: the first strict row-major maximum over
+ *   the in-band interior cells ((1, 1) is always one); target_begin = gj + 1.
+ *   Semi-global: the reference's scan over in-band cells only -- column m
+ *   with i ascending, then row n, strict '>' -- and the trailing I / D run to
+ *   (n, m) as today.  Traceback, reversal, RLE and "1\0" are unchanged.
+ *   Degenerate pairs (n == 0 or m == 0): today's closed forms.
+ * With every cell the unbanded walk visits in band, the results equal the
+ * unbanded ones; a banded score is never above the unbanded score.
+ * Range: (max qlen + max tlen + 2) * max(|match|, |mismatch|, |gap|) must be
+ * < 2^26, else TA_ERR_RANGE (the affine extension's rule).
+ */
+typedef struct ta_banded_plan ta_banded_plan;
+
+/* As ta_plan_create, with band[n_pairs] (host array, copied).  Codes are kept
+ * only for the columns each 1024-row pass sweeps.  flags: 0. */
+int ta_banded_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* query_len_host,
+                          const uint32_t* target_len_host, const uint32_t* band_host, int type, int match,
+                          int mismatch, int gap, int want_cigar, uint64_t workspace_budget, uint32_t flags,
+                          ta_banded_plan** out);
+void ta_banded_plan_destroy(ta_banded_plan* plan);
+uint64_t ta_banded_plan_cigar_slots_bytes(const ta_banded_plan* plan);
+uint64_t ta_banded_plan_workspace_bytes(const ta_banded_plan* plan);
+uint32_t ta_banded_plan_chunks(const ta_banded_plan* plan);
+int ta_banded_plan_pair_chunks(const ta_banded_plan* plan, uint32_t* chunk_of_pair);
+/* Diagnostics: the in-band interior cells of all pairs (the numerator of a
+ * cell-update rate) and the cells the kernels sweep (each pass's column range
+ * times its rows). */
+uint64_t ta_banded_plan_band_cells(const ta_banded_plan* plan);
+uint64_t ta_banded_plan_swept_cells(const ta_banded_plan* plan);
+/* Enqueue the whole batch / one chunk's fill / one chunk's traceback on hip_stream. */
+int ta_banded_plan_execute(ta_banded_plan* plan, const ta_device_io* io, void* hip_stream);
+int ta_banded_plan_execute_fill(ta_banded_plan* plan, const ta_device_io* io, void* hip_stream, uint32_t chunk);
+int ta_banded_plan_execute_traceback(ta_banded_plan* plan, const ta_device_io* io, void* hip_stream,
+                                     uint32_t chunk);
+/* As ta_plan_check (the banded kernels have no failure to report: TA_OK). */
+int ta_banded_plan_check(ta_banded_plan* plan);
+/* As ta_plan_annotate, for a banded plan's execution. */
+int ta_banded_plan_annotate(ta_banded_plan* plan, const ta_device_io* io, const ta_annotate_io* out,
+                            void* hip_stream);
+
+/* Host-memory batch with a band per pair: ta_align_batch plus band[n_pairs]. */
+int ta_align_batch_banded(ta_context* ctx, uint32_t n_pairs, const char* query_bytes, const uint64_t* query_off,
+                          const uint32_t* query_len, const char* target_bytes, const uint64_t* target_off,
+                          const uint32_t* target_len, const uint32_t* band, int type, int match, int mismatch,
+                          int gap, int want_cigar, int32_t* score, uint32_t* target_begin, char* cigar_arena,
+                          uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len);
+
 #ifdef __cplusplus
 }
 #endif

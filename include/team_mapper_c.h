@@ -131,6 +131,17 @@ int tm_map_batch_x(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const
                    uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags,
                    ta_pair_info* info);
 
+/* tm_map_batch_x with a band: every window is aligned by the banded extension
+ * of libteam_alignment (ta_banded_plan_*, team_align_c.h) with this band, so
+ * work and code workspace grow with window length x band.  A band that holds
+ * a window's whole matrix (band >= its longer side) gives tm_map_batch_x's
+ * results for it.  tm_map_batch_x itself never takes this path. */
+int tm_map_batch_band(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes, const uint64_t* off,
+                      const uint32_t* len, const tm_options* opt, uint8_t* mapped, uint8_t* strand_fwd,
+                      uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end, int32_t* score,
+                      char* cigar_arena, uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
+                      uint32_t flags, ta_pair_info* info, uint32_t band);
+
 /* Wall time (ms) of the last tm_map_batch on this context, per stage:
  * [0] read upload, [1] minimizers, [2] seed matching, [3] FindLIS chaining,
  * [4] windows + alignment plan (host), [5] alignment (fill + traceback),
@@ -140,7 +151,8 @@ int tm_stage_times(const tm_context* ctx, double* ms, uint32_t n, uint64_t* alig
 
 /* The alignment plan of the last tm_map_batch: out[0] pairs, [1] chunks,
  * [2] pairs on the packed int16 fills (dual + flexible), [3] pairs on the
- * flexible fill, [4] code workspace bytes (ta_plan_* of libteam_alignment). */
+ * flexible fill, [4] code workspace bytes (ta_plan_* of libteam_alignment).
+ * After a banded batch: pairs, chunks, 0, 0, workspace bytes. */
 int tm_align_plan_stats(const tm_context* ctx, uint64_t out[5]);
 
 /*
@@ -155,6 +167,9 @@ int tm_map_files(const char* reference_path, const char* reads_path, const tm_op
  * want_cigar).  flags 0: tm_map_files exactly. */
 int tm_map_files_x(const char* reference_path, const char* reads_path, const tm_options* opt, const char* out_path,
                    int device, uint32_t flags);
+/* tm_map_files_x with a band for every window (team_mapper_amd --band N). */
+int tm_map_files_band(const char* reference_path, const char* reads_path, const tm_options* opt, const char* out_path,
+                      int device, uint32_t flags, uint32_t band);
 
 #ifdef __cplusplus
 }
