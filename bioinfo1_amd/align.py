@@ -105,6 +105,11 @@ def lib() -> C.CDLL:
                                     C.c_void_p, C.c_void_p]
     L.ta_plan_execute_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.ta_plan_execute_traceback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ta_pipeline_create.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ta_pipeline_create_affine.argtypes = L.ta_pipeline_create.argtypes
+    L.ta_pipeline_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u32p]
+    L.ta_pipeline_destroy.argtypes = [C.c_void_p]
+    L.ta_pipeline_destroy.restype = None
     # affine-gap extension (include/team_align_c.h, no reference counterpart)
     L.ta_align_batch_affine.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64p, u32p, C.c_void_p, u64p, u32p,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, u32p, C.c_void_p,
@@ -174,6 +179,8 @@ ABI_SYMBOLS = [
     "ta_server_create", "ta_server_destroy", "ta_server_fits", "ta_server_align", "ta_server_running",
     "ta_server_last_times", "ta_server_pause", "ta_server_resume",
     "ta_plan_annotate", "ta_affine_plan_annotate",
+    "ta_plan_context", "ta_affine_plan_context", "ta_context_device",
+    "ta_pipeline_create", "ta_pipeline_create_affine", "ta_pipeline_step", "ta_pipeline_destroy",
 ]
 # The banded extension's symbols (checked by tests/test_banded_ref.py).
 BANDED_ABI_SYMBOLS = [
@@ -730,8 +737,11 @@ class DevicePipeline:
     DevicePlan on its own Aligner context: the context owns the workspace the
     fill writes and the walk reads, and ta_plan_execute_fill / _traceback order
     one context's launches across streams (a slot's traceback waits for its
-    fill, its next fill for that traceback).  Fills run on the pipeline's fill
-    stream, tracebacks on its high-priority walk stream, and the caller's
+    fill, its next fill for that traceback).  The streams, events and
+    dependencies are the library's (ta_pipeline_* of team_align_c.h,
+    csrc/ta_pipeline.cpp): each slot's fills run on a fill stream of the slot's
+    own, so a fill also overlaps the tail of the fill before it; tracebacks on
+    a high-priority walk stream; and the caller's
     current stream waits for each step's traceback, so whatever the caller
     enqueues after step() on its stream (a compaction, a gather, the next
     upload into this step's input buffers) follows it; a slot's next fill also
@@ -744,17 +754,23 @@ class DevicePipeline:
     pipeline was built, or synchronised): waiting on the caller's stream would
     also wait for the previous step's traceback and serialise the pipeline.  A
     step without inputs realigns the slot's last batch (at construction: the
-    shared first batch).  Memory: ``depth`` workspaces."""
+    shared first batch).  Memory: ``depth`` workspaces (3 by default)."""
 
-    def __init__(self, device: int, batch, type, match, mismatch, gap, want_cigar=True, depth: int = 2,
+    def __init__(self, device: int, batch, type, match, mismatch, gap, want_cigar=True, depth: int = 3,
                  workspace_budget: int = 0, gap_open=None, flags: int = 0, inputs=None, first=None):
         """first: an existing DevicePlan (on its own Aligner) to use as slot 0;
-        the other slots then start on its inputs."""
+        the other slots then start on its inputs.  depth: the slots (>= 2).
+        At 2, fill k+2 waits for walk k, which ends only shortly before fill
+        k+1 does, and every other step leaves the chip without a fill; at 3
+        a fill is always queued behind the running one (DESIGN 3.12 has the
+        measurements; 4 was slower).  A caller that rotates its batches to
+        check the pipeline wants a count coprime with the depth, or every
+        slot realigns the batch it held last."""
         import torch
 
         self.torch = torch
         self.dev = torch.device("cuda", device)
-        self.aligners, self.plans = [], []
+        self.aligners, self.plans, self.k = [], [], 0
         for k in range(depth):
             if k == 0 and first is not None:
                 self.plans.append(first)
@@ -766,54 +782,49 @@ class DevicePipeline:
             self.plans.append(DevicePlan(al, batch, type, match, mismatch, gap, want_cigar,
                                          workspace_budget=workspace_budget, gap_open=gap_open, flags=flags,
                                          inputs=shared))
-        # the tracebacks on a high-priority stream: HIP gives it a hardware queue
-        # of its own (streams of one priority share GPU_MAX_HW_QUEUES queues, and
-        # the kernels of one queue run one after the other)
-        self.fill = torch.cuda.Stream(self.dev)
-        self.walk = torch.cuda.Stream(self.dev, priority=-1)
-        for st in (self.fill, self.walk):
-            st.wait_stream(torch.cuda.current_stream(self.dev))  # (the inputs' uploads)
-        self.walked = [torch.cuda.Event() for _ in range(depth)]
-        self.done = [torch.cuda.Event() for _ in range(depth)]
-        self.used = [False] * depth
-        self.k = 0
-        self.last = None
+        L = lib()
+        handles = (C.c_void_p * len(self.plans))(*[p._h for p in self.plans])
+        h = C.c_void_p()
+        create = L.ta_pipeline_create_affine if self.plans[0].affine else L.ta_pipeline_create
+        r = create(handles, len(self.plans), C.byref(h))
+        if r != TA_OK:
+            msg = L.ta_last_error(self.plans[0]._ctx).decode()
+            for p in self.plans[1 if first is not None else 0:]:  # (a caller's ``first`` stays open)
+                p.close()
+            for al in self.aligners:
+                al.close()
+            if r == TA_ERR_ARG:
+                raise ValueError(msg or "ta_pipeline_create: invalid argument")
+            raise DeviceError(f"{L.ta_status_string(r).decode()}: {msg}")
+        self._h = h
 
     @property
     def chunks(self):
         return self.plans[0].chunks
 
     def step(self, inputs=None, ready=None):
-        """Enqueue one batch: its fill on the fill stream, its traceback on the
-        walk stream (the current stream waits for it).  inputs: this batch's
+        """Enqueue one batch (ta_pipeline_step): its fill on the slot's fill
+        stream, its traceback on the walk stream (the current stream waits for
+        it).  inputs: this batch's
         (query bytes, query offsets, target bytes, target offsets) tensors in
         HBM, same shapes as planned; ready: an event the fill waits for first
-        (None: the inputs are resident).  Returns the slot's
+        (None: the inputs are resident); ``ready`` without ``inputs`` is a
+        ValueError.  Returns the slot's
         DevicePlan (its results are ready on the current stream after the call;
         the inputs may be overwritten by work enqueued on it after the call)."""
-        torch = self.torch
-        cur = torch.cuda.current_stream(self.dev)
-        depth = len(self.plans)
-        if self.last is not None:  # the previous slot's traceback and what the caller queued after it
-            self.done[self.last].record(cur)
-        i = self.k % depth
-        self.k += 1
-        plan = self.plans[i]
-        if self.used[i]:
-            self.fill.wait_event(self.done[i])
+        if ready is not None and inputs is None:
+            raise ValueError("DevicePipeline.step: ready without inputs (the event belongs to an upload of inputs)")
+        plan = self.plans[self.k % len(self.plans)]  # (the library's rotation: step k on slot k % depth)
         if inputs is not None:
             plan.set_inputs(inputs)
-            if ready is not None:
-                self.fill.wait_event(ready)
-        for c in range(plan.chunks):
-            with torch.cuda.stream(self.fill):
-                plan.run_fill(c)
-            with torch.cuda.stream(self.walk):
-                plan.run_traceback(c)  # (waits for the fill: the slot's context orders them)
-        self.walked[i].record(self.walk)
-        cur.wait_event(self.walked[i])
-        self.used[i] = True
-        self.last = i
+        cur = self.torch.cuda.current_stream(self.dev)
+        slot = C.c_uint32()
+        ev = C.c_void_p(ready.cuda_event) if ready is not None else None
+        r = lib().ta_pipeline_step(self._h, C.byref(plan.io), ev, C.c_void_p(cur.cuda_stream), C.byref(slot))
+        if r != TA_OK:
+            _raise(r, plan._ctx)
+        assert self.plans[slot.value] is plan
+        self.k += 1
         return plan
 
     def check(self):
@@ -821,6 +832,9 @@ class DevicePipeline:
             p.check()
 
     def close(self):
+        if getattr(self, "_h", None):  # (before the plans and contexts it refers to)
+            lib().ta_pipeline_destroy(self._h)
+            self._h = None
         for p in self.plans:
             p.close()
         for al in self.aligners:

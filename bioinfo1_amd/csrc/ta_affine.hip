@@ -1401,6 +1401,7 @@ uint64_t ta_affine_plan_workspace_bytes(const ta_affine_plan* pl) {
     return pl ? pl->h.ws_ptr_entries * sizeof(uint2) + pl->h.ws_bnd_entries * sizeof(int2) : 0;
 }
 uint32_t ta_affine_plan_chunks(const ta_affine_plan* pl) { return pl ? (uint32_t)pl->h.chunks.size() : 0; }
+ta_context* ta_affine_plan_context(const ta_affine_plan* pl) { return pl ? pl->ctx : nullptr; }
 uint32_t ta_affine_plan_dual_pairs(const ta_affine_plan* pl) { return pl ? (uint32_t)pl->h.duals.size() : 0; }
 
 int ta_affine_plan_pair_chunks(const ta_affine_plan* pl, uint32_t* chunk_of_pair) {

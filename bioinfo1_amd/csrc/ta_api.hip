@@ -18,6 +18,7 @@
 #include "ta_context.h"
 #include "ta_host_batch.h"
 #include "ta_internal.h"
+#include "ta_pipeline_internal.h"
 #include "ta_planner.h"
 
 using ta_host::fail;
@@ -275,12 +276,15 @@ int exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, b
             }
             if (ch.dcount && ch.fcount) TA_HIP(ctx, hipStreamWaitEvent(s, ctx->ev_join2, 0));
             // couples the packed kernels handed back ('-' in a query): int32
-            // fill, wave count read on the device (grid sized for all of them)
+            // fill, wave count read on the device by a small fixed grid whose
+            // waves stride over it (usually there is none, and a grid sized for
+            // every pair only stands between this fill and what follows it)
             ta::FillArgs f = a;
             f.order = fb_list;
             f.begin = 0;
             f.count = 2 * (ch.dcount + ch.fcount);
             f.count_dev = fb_count;
+            f.max_blocks = ctx->cu_count;  // (a block per CU: 4 * cu_count waves for a batch full of '-')
             TA_HIP(ctx, ta::launch_fill(h.type, h.want_cigar, h.wide, f, s));
         }
         if (ch.scount && (ch.dcount || ch.fcount)) {  // join the aux stream
@@ -504,6 +508,11 @@ uint64_t ta_plan_workspace_bytes(const ta_plan* pl) {
     return (h.ws_ptr_dwords + h.ws_bnd_words) * 4ull + runs;
 }
 uint32_t ta_plan_chunks(const ta_plan* pl) { return pl ? (uint32_t)pl->h.chunks.size() : 0; }
+ta_context* ta_plan_context(const ta_plan* pl) { return pl ? pl->ctx : nullptr; }
+int ta_context_device(const ta_context* ctx) { return ctx ? ctx->device : -1; }
+void ta_context_set_error(ta_context* ctx, const char* message) {
+    if (ctx) ctx->last_error = message ? message : "";
+}
 uint32_t ta_plan_dual_pairs(const ta_plan* pl) { return pl ? pl->h.n_dual_pairs : 0; }
 uint32_t ta_plan_flex_pairs(const ta_plan* pl) { return pl ? (uint32_t)pl->h.flexes.size() : 0; }
 int ta_plan_fused(const ta_plan* pl) { return pl && pl->h.fused ? 1 : 0; }

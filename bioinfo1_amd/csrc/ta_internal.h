@@ -49,6 +49,7 @@ struct FillArgs {
     uint32_t* fb_list;
     uint32_t* fb_count;
     const uint32_t* count_dev;
+    uint32_t max_blocks;  // with count_dev, non-zero: fill_back_kernel in a grid of at most this many blocks
     // flexible fill, one wave per (couple, pass): waves take tickets in launch
     // order, so every pass a wave waits on is already held by a running wave
     const uint32_t* task_off;  // per flex couple (plan order): its first task; [w + 1] - [w] = passes

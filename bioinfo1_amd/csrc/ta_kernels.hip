@@ -455,6 +455,19 @@ __global__ __launch_bounds__(kBlock) void fill_kernel(FillArgs a) {
     fill_pair<MODE, CIGAR, WIDE>(a, a.order ? a.order[a.begin + widx] : a.begin + widx, lane);
 }
 
+// The hand-back launch (count_dev: the couples a packed fill handed back,
+// usually none): a fixed grid of at most a.max_blocks blocks whose waves
+// stride over the count on the device.  A kernel of its own, so that
+// fill_kernel stays one pair per wave with no loop around it.
+template <int MODE, bool CIGAR, bool WIDE>
+__global__ __launch_bounds__(kBlock) void fill_back_kernel(FillArgs a) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t count = *a.count_dev;  // wave-uniform
+    const uint32_t stride = gridDim.x * kWavesPerBlock;
+    for (uint32_t widx = wave_id(); widx < count; widx += stride)
+        fill_pair<MODE, CIGAR, WIDE>(a, a.order[a.begin + widx], lane);
+}
+
 // The pipelined int32 fill: one wave per (pair, pass) of a chunk's singles
 // (order = the plan's singles).  A wave takes the next ticket; the tasks are
 // pass-major (every pair's pass 0, then every pass 1, ...; the planner's
@@ -985,6 +998,12 @@ hipError_t launch_fill_mode<TA_FILL_MODE, (TA_FILL_CIGAR != 0)>(bool wide, const
     constexpr bool CIGAR = TA_FILL_CIGAR != 0;
     if (!a.count) return hipSuccess;
     const dim3 g = grid_for(a.count), b(kBlock);
+    if (a.count_dev && a.max_blocks) {  // the hand-back launch: a fixed grid, strided
+        const dim3 gb(std::min<uint32_t>(g.x, a.max_blocks));
+        if (MODE == kLocal && wide) hipLaunchKernelGGL((fill_back_kernel<MODE, CIGAR, MODE == kLocal>), gb, b, 0, s, a);
+        else hipLaunchKernelGGL((fill_back_kernel<MODE, CIGAR, false>), gb, b, 0, s, a);
+        return hipGetLastError();
+    }
     if (a.tasks64) {  // one wave per (pair, pass), then the fold of the passes
         if (a.n_tasks) {
             const dim3 gt = grid_for(a.n_tasks);

@@ -1,0 +1,207 @@
+// bioinfo1_amd/csrc/ta_pipeline.cpp -- ta_pipeline_* of include/team_align_c.h:
+// the dependency structure of batches aligned back to back.
+//
+// Host C++ over the C ABI and the HIP runtime's streams and events only: no
+// kernel, no device-side polling.  What it relies on from the plans' drivers:
+// an execution on another stream than its context's previous one first waits
+// for that one (ta_context.h stream_enter / stream_leave), so a slot's
+// traceback on the walk stream follows its fill on the slot's fill stream, and
+// a chunk's fill the traceback of the chunk before it (one workspace).
+//
+// Streams: ONE FILL STREAM PER SLOT.  Fill k+2 (slot s) waits for slot s's
+// done event only -- walk k and what the caller queued after it -- never for
+// fill k+1, which runs on another slot's stream: when fill k+1's last blocks
+// run alone on a mostly idle chip (they could not become resident while walk
+// k held registers), fill k+2's blocks take the free CUs.
+#ifndef __HIP_PLATFORM_AMD__
+#define __HIP_PLATFORM_AMD__ 1
+#endif
+#include <hip/hip_runtime_api.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/team_align_c.h"
+#include "ta_pipeline_internal.h"
+
+namespace {
+
+// The plan family's entry points behind a slot (linear-gap or affine plans).
+struct Ops {
+    ta_context* (*context)(const void*);
+    uint32_t (*chunks)(const void*);
+    int (*fill)(void*, const ta_device_io*, void*, uint32_t);
+    int (*walk)(void*, const ta_device_io*, void*, uint32_t);
+};
+
+const Ops kLinear = {
+    [](const void* p) { return ta_plan_context(static_cast<const ta_plan*>(p)); },
+    [](const void* p) { return ta_plan_chunks(static_cast<const ta_plan*>(p)); },
+    [](void* p, const ta_device_io* io, void* s, uint32_t c) {
+        return ta_plan_execute_fill(static_cast<ta_plan*>(p), io, s, c);
+    },
+    [](void* p, const ta_device_io* io, void* s, uint32_t c) {
+        return ta_plan_execute_traceback(static_cast<ta_plan*>(p), io, s, c);
+    },
+};
+
+const Ops kAffine = {
+    [](const void* p) { return ta_affine_plan_context(static_cast<const ta_affine_plan*>(p)); },
+    [](const void* p) { return ta_affine_plan_chunks(static_cast<const ta_affine_plan*>(p)); },
+    [](void* p, const ta_device_io* io, void* s, uint32_t c) {
+        return ta_affine_plan_execute_fill(static_cast<ta_affine_plan*>(p), io, s, c);
+    },
+    [](void* p, const ta_device_io* io, void* s, uint32_t c) {
+        return ta_affine_plan_execute_traceback(static_cast<ta_affine_plan*>(p), io, s, c);
+    },
+};
+
+int fail(ta_context* ctx, int code, const std::string& msg) {
+    ta_context_set_error(ctx, msg.c_str());
+    return code;
+}
+
+#define TP_HIP(ctx, expr)                                                                     \
+    do {                                                                                      \
+        hipError_t e_ = (expr);                                                               \
+        if (e_ != hipSuccess)                                                                 \
+            return fail((ctx), TA_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+}  // namespace
+
+struct ta_pipeline {
+    const Ops* ops = nullptr;
+    int device = 0;
+    std::vector<void*> slots;
+    std::vector<ta_context*> ctxs;
+    // created at the first step (each stream takes one of the process's few hardware queues)
+    std::vector<hipStream_t> fill;  // one per slot
+    hipStream_t walk = nullptr;     // high priority: a hardware queue of its own beside the fills'
+    // done[s]: recorded on the caller's stream at the step after slot s's, so it covers
+    // slot s's traceback and what the caller queued after it; walked[s]: slot s's traceback;
+    // start: the caller's stream at the first step (a slot's first fill follows it)
+    std::vector<hipEvent_t> done, walked;
+    hipEvent_t start = nullptr;
+    std::vector<bool> used;
+    uint64_t k = 0;
+    int last = -1;
+};
+
+namespace {
+
+int create(const Ops& ops, void* const* slots, uint32_t depth, ta_pipeline** out) {
+    if (!out) return TA_ERR_ARG;
+    *out = nullptr;
+    if (!slots || !depth || !slots[0]) return TA_ERR_ARG;
+    ta_context* c0 = ops.context(slots[0]);
+    if (!c0) return TA_ERR_ARG;
+    if (depth < 2) return fail(c0, TA_ERR_ARG, "ta_pipeline_create: depth must be at least 2");
+    for (uint32_t a = 0; a < depth; ++a) {
+        ta_context* ca = slots[a] ? ops.context(slots[a]) : nullptr;
+        if (!ca) return fail(c0, TA_ERR_ARG, "ta_pipeline_create: null slot");
+        if (ta_context_device(ca) != ta_context_device(c0))
+            return fail(c0, TA_ERR_ARG, "ta_pipeline_create: slots on different devices");
+        for (uint32_t b = 0; b < a; ++b)
+            if (ops.context(slots[b]) == ca)
+                return fail(c0, TA_ERR_ARG, "ta_pipeline_create: two slots share a context (each needs its own workspace)");
+    }
+    auto* p = new ta_pipeline();
+    p->ops = &ops;
+    p->device = ta_context_device(c0);
+    p->slots.assign(slots, slots + depth);
+    for (uint32_t a = 0; a < depth; ++a) p->ctxs.push_back(ops.context(slots[a]));
+    p->fill.assign(depth, nullptr);
+    p->done.assign(depth, nullptr);
+    p->walked.assign(depth, nullptr);
+    p->used.assign(depth, false);
+    *out = p;
+    return TA_OK;
+}
+
+int lazy_stream(ta_context* ctx, hipStream_t& s, int priority) {
+    if (s) return TA_OK;
+    if (hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority) != hipSuccess) {
+        s = nullptr;
+        return fail(ctx, TA_ERR_DEVICE, "ta_pipeline_step: hipStreamCreateWithPriority failed");
+    }
+    return TA_OK;
+}
+
+int lazy_event(ta_context* ctx, hipEvent_t& e) {
+    if (e) return TA_OK;
+    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+        e = nullptr;
+        return fail(ctx, TA_ERR_DEVICE, "ta_pipeline_step: hipEventCreateWithFlags failed");
+    }
+    return TA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ta_pipeline_create(ta_plan* const* slots, uint32_t depth, ta_pipeline** out) {
+    return create(kLinear, reinterpret_cast<void* const*>(slots), depth, out);
+}
+
+int ta_pipeline_create_affine(ta_affine_plan* const* slots, uint32_t depth, ta_pipeline** out) {
+    return create(kAffine, reinterpret_cast<void* const*>(slots), depth, out);
+}
+
+int ta_pipeline_step(ta_pipeline* p, const ta_device_io* io, void* ready_event, void* caller_stream,
+                     uint32_t* slot_out) {
+    if (!p) return TA_ERR_ARG;
+    const uint32_t depth = (uint32_t)p->slots.size();
+    const uint32_t i = (uint32_t)(p->k % depth);
+    ta_context* ctx = p->ctxs[i];
+    if (!io) return fail(ctx, TA_ERR_ARG, "ta_pipeline_step: null io");
+    hipStream_t cur = static_cast<hipStream_t>(caller_stream);
+    TP_HIP(ctx, hipSetDevice(p->device));
+    if (!p->walk) {
+        int least = 0, greatest = 0;
+        TP_HIP(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        if (int r = lazy_stream(ctx, p->walk, greatest)) return r;
+    }
+    if (int r = lazy_stream(ctx, p->fill[i], 0)) return r;
+    if (int r = lazy_event(ctx, p->done[i])) return r;
+    if (int r = lazy_event(ctx, p->walked[i])) return r;
+    if (!p->start) {
+        if (int r = lazy_event(ctx, p->start)) return r;
+        TP_HIP(ctx, hipEventRecord(p->start, cur));
+    }
+    // the previous slot's traceback and what the caller queued after it
+    if (p->last >= 0) TP_HIP(ctx, hipEventRecord(p->done[p->last], cur));
+    if (slot_out) *slot_out = i;
+    void* plan = p->slots[i];
+    TP_HIP(ctx, hipStreamWaitEvent(p->fill[i], p->used[i] ? p->done[i] : p->start, 0));
+    if (ready_event) TP_HIP(ctx, hipStreamWaitEvent(p->fill[i], static_cast<hipEvent_t>(ready_event), 0));
+    const uint32_t chunks = p->ops->chunks(plan);
+    for (uint32_t c = 0; c < chunks; ++c) {
+        if (int r = p->ops->fill(plan, io, p->fill[i], c)) return r;
+        if (int r = p->ops->walk(plan, io, p->walk, c)) return r;  // (after the fill: the slot's context orders them)
+    }
+    TP_HIP(ctx, hipEventRecord(p->walked[i], p->walk));
+    TP_HIP(ctx, hipStreamWaitEvent(cur, p->walked[i], 0));
+    p->used[i] = true;
+    p->last = (int)i;
+    ++p->k;
+    return TA_OK;
+}
+
+void ta_pipeline_destroy(ta_pipeline* p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    // (destroying a stream or an event with work pending is deferred by the runtime until it is done)
+    for (hipStream_t s : p->fill)
+        if (s) (void)hipStreamDestroy(s);
+    if (p->walk) (void)hipStreamDestroy(p->walk);
+    for (hipEvent_t e : p->done)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : p->walked)
+        if (e) (void)hipEventDestroy(e);
+    if (p->start) (void)hipEventDestroy(p->start);
+    delete p;
+}
+
+}  // extern "C"

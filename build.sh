@@ -61,6 +61,9 @@ cc "$B/ta_server.o" "$CS/ta_server.cpp" "$HIPCC" "${FLAGS[@]}" -x hip -c "$CS/ta
 cc "$B/shim.o" "$CS/team_alignment_shim.cpp" "$HIPCC" "${FLAGS[@]}" -x c++ -c "$CS/team_alignment_shim.cpp"
 # host planner: plain C++ (also built with g++ under ASan/UBSan/TSan by tests/test_host_sanitizers.py)
 cc "$B/ta_planner.o" "$CS/ta_planner.cpp" g++ -O2 -std=c++17 -fPIC -Wall -c "$CS/ta_planner.cpp"
+# the batch pipeline (ta_pipeline_*): host C++ over the C ABI and the HIP runtime's streams and events
+# (also built against a recording stub of both by tests/test_pipeline_order.py)
+cc "$B/ta_pipeline.o" "$CS/ta_pipeline.cpp" g++ -O2 -std=c++17 -fPIC -Wall -I"$(dirname "$(dirname "$HIPCC")")/include" -c "$CS/ta_pipeline.cpp"
 # mapper stages (libteam_mapper.so) and the team_mapper_amd CLI
 if [ "${TA_LIB_ONLY:-0}" != 1 ]; then
 for f in tm_minimizers tm_match tm_chain; do
@@ -72,7 +75,7 @@ done
 cc "$B/tm_main.o" "$CS/tm_main.cpp" "$HIPCC" "${FLAGS[@]}" -x c++ -c "$CS/tm_main.cpp"
 fi
 for p in "${pids[@]}"; do wait "$p"; done
-"$HIPCC" -shared -fPIC --offload-arch=gfx950 "$B"/ta_fill_{0,1,2}{0,1}.o "$B"/ta_dual_{0,1,2}{0,1}.o "$B/ta_dual_blk.o" "$B"/ta_dual_ck_{0,1,2}.o "$B/ta_walk_ck.o" "$B"/ta_flex_{0,1,2}{0,1}.o "$B"/ta_flex_ck_{0,1,2}.o "$B/ta_misc.o" "$B/ta_annotate.o" "$B/ta_affine.o" "$B/ta_banded.o" "$B/ta_api.o" "$B/ta_server.o" "$B/ta_planner.o" "$B/shim.o" \
+"$HIPCC" -shared -fPIC --offload-arch=gfx950 "$B"/ta_fill_{0,1,2}{0,1}.o "$B"/ta_dual_{0,1,2}{0,1}.o "$B/ta_dual_blk.o" "$B"/ta_dual_ck_{0,1,2}.o "$B/ta_walk_ck.o" "$B"/ta_flex_{0,1,2}{0,1}.o "$B"/ta_flex_ck_{0,1,2}.o "$B/ta_misc.o" "$B/ta_annotate.o" "$B/ta_affine.o" "$B/ta_banded.o" "$B/ta_api.o" "$B/ta_server.o" "$B/ta_planner.o" "$B/ta_pipeline.o" "$B/shim.o" \
   -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib -o "$OUT"
 if [ "${TA_LIB_ONLY:-0}" = 1 ]; then echo "built $OUT"; exit 0; fi
 PKG="$ROOT/bioinfo1_amd"

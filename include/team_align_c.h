@@ -239,6 +239,42 @@ int ta_plan_check(ta_plan* plan);
 int ta_plan_execute_fill(ta_plan* plan, const ta_device_io* io, void* hip_stream, uint32_t chunk);
 int ta_plan_execute_traceback(ta_plan* plan, const ta_device_io* io, void* hip_stream, uint32_t chunk);
 
+/* The context a plan was created on, and a context's device. */
+ta_context* ta_plan_context(const ta_plan* plan);
+int ta_context_device(const ta_context* ctx);
+
+/*
+ * Batches back to back, batch k's traceback beside batch k+1's fill, and a
+ * fill beside the tail of the fill before it.  The slots are `depth` (>= 2)
+ * plans of the same shapes, each on a context of its own (a context owns the
+ * workspace the fill writes and the walk reads) and all on one device;
+ * TA_ERR_ARG otherwise, with the reason in ta_last_error of the first slot's
+ * context.  The pipeline owns one fill stream per slot, one high-priority
+ * walk stream and its events, all created at the first step; the plans and
+ * contexts stay the caller's and outlive the pipeline.
+ *
+ * ta_pipeline_step enqueues the next batch on the next slot in turn (step k
+ * uses slot k % depth; *slot_out, when not NULL, receives it) and returns:
+ *   - on the slot's fill stream: a wait for whatever the caller had enqueued
+ *     on `caller_stream` up to the step after this slot's previous one (its
+ *     previous traceback included), a wait for `ready_event` (a hipEvent_t
+ *     recorded after the upload of this batch's inputs; NULL: the inputs were
+ *     resident before the pipeline's first step, or the host waited for them)
+ *     and every chunk's fill;
+ *   - on the walk stream: every chunk's traceback (after its fill);
+ *   - on `caller_stream`: a wait for that traceback, so what the caller
+ *     enqueues there after the call sees this step's results, and may
+ *     overwrite its inputs.
+ * No fill waits for another slot's fill.  Errors (TA_ERR_ARG for a null
+ * argument, TA_ERR_DEVICE) leave their message in ta_last_error of the slot's
+ * context; argument errors enqueue nothing.  One thread at a time per pipeline.
+ */
+typedef struct ta_pipeline ta_pipeline;
+int ta_pipeline_create(ta_plan* const* slots, uint32_t depth, ta_pipeline** out);
+int ta_pipeline_step(ta_pipeline* pipe, const ta_device_io* io, void* ready_event, void* caller_stream,
+                     uint32_t* slot_out);
+void ta_pipeline_destroy(ta_pipeline* pipe);
+
 /* Pack n_pairs CIGARs from their slots (device: cigar_slots, cigar_start,
  * cigar_len as written by an execution) back to back into dst (device):
  * pair p's bytes go to dst[dst_off[p] ..).  Enqueued on hip_stream.  For a
@@ -337,6 +373,9 @@ int ta_affine_plan_execute_traceback(ta_affine_plan* plan, const ta_device_io* i
 /* As ta_plan_check: TA_ERR_DEVICE when a pass hand-off poll of the packed
  * affine fill (one wave per couple and pass) gave up; clears the flag. */
 int ta_affine_plan_check(ta_affine_plan* plan);
+/* As ta_plan_context; and a ta_pipeline (above) whose slots are affine plans. */
+ta_context* ta_affine_plan_context(const ta_affine_plan* plan);
+int ta_pipeline_create_affine(ta_affine_plan* const* slots, uint32_t depth, ta_pipeline** out);
 /* As ta_plan_annotate, for an affine plan's execution. */
 int ta_affine_plan_annotate(ta_affine_plan* plan, const ta_device_io* io, const ta_annotate_io* out,
                             void* hip_stream);

@@ -1,0 +1,69 @@
+"""The pipelined steps of a rocprofv3 kernel trace (bench.py's default run, no --serial), per steady-state step:
+start and end of the checkpoint fill, of the hand-back int32 fill launch, of the walk and of the formatter, the
+idle gap between one fill's end and the next fill's start, how far a fill reaches into the fill before it, and
+the step period.  Usage: pipeline_trace_summary.py <run_kernel_trace.csv> <out.json> [steps, default 20]"""
+import csv
+import json
+import os
+import statistics
+import sys
+
+rows = list(csv.DictReader(open(sys.argv[1])))
+steps = int(sys.argv[3]) if len(sys.argv) > 3 else 20
+k = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r["Queue_Id"],
+            int(r["Grid_Size_X"]) // max(int(r["Workgroup_Size_X"]), 1)) for r in rows)
+
+
+def of(sub, not_sub=None):
+    return [x for x in k if sub in x[2] and not (not_sub and not_sub in x[2])]
+
+
+fills = of("dual_fill_ck_kernel")
+walks = of("traceback_ck_kernel")
+fmts = of("format_runs_kernel")
+# the hand-back launch right after a checkpoint fill on its queue: fill_back_kernel (before it: the int32 fill_kernel)
+backs = of("fill_back_kernel") or [x for x in of("fill_kernel", "dual_fill") if "fill_pipe" not in x[2]]
+fills = fills[-steps - 1:]  # the last steps of the timed loop: steady state
+t0 = fills[0][0]
+
+
+def us(a):
+    return round(a / 1e3, 1)
+
+
+def stat(v):
+    v = [x / 1e3 for x in v]
+    return {"median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1)} if v else None
+
+
+def inside(xs):
+    return [x for x in xs if t0 <= x[0] <= fills[-1][1]]
+
+
+per_step = []
+for a, b in zip(fills, fills[1:]):
+    back = next((x for x in backs if x[0] >= a[1] - 1000 and x[3] == a[3] and x[0] < a[1] + 2_000_000), None)
+    walk = next((x for x in walks if x[0] >= a[1] - 1000), None)
+    fmt = next((x for x in fmts if walk and x[0] >= walk[1] - 1000), None)
+    per_step.append({"fill": [us(a[0] - t0), us(a[1] - t0)], "fill_queue": a[3],
+                     "hand_back": [us(back[0] - t0), us(back[1] - t0)] if back else None,
+                     "walk": [us(walk[0] - t0), us(walk[1] - t0)] if walk else None,
+                     "format": [us(fmt[0] - t0), us(fmt[1] - t0)] if fmt else None,
+                     "next_fill_start_minus_fill_end_us": us(b[0] - a[1])})
+gaps = [b[0] - a[1] for a, b in zip(fills, fills[1:])]
+out = {"trace": os.path.basename(os.path.dirname(os.path.abspath(sys.argv[1]))), "steps": len(per_step),
+       "fill_queues": sorted({x[3] for x in fills}), "walk_queues": sorted({x[3] for x in inside(walks)}),
+       "fill_blocks": fills[0][4], "hand_back_blocks": sorted({x[4] for x in inside(backs)}),
+       "walk_blocks": sorted({x[4] for x in inside(walks)}),
+       "period": stat([b[0] - a[0] for a, b in zip(fills, fills[1:])]),
+       "fill": stat([e - s for s, e, *_ in fills]),
+       "hand_back": stat([e - s for s, e, *_ in inside(backs)]),
+       "walk": stat([e - s for s, e, *_ in inside(walks)]),
+       "format": stat([e - s for s, e, *_ in inside(fmts)]),
+       # > 0: the GPU had no fill for that long; < 0: the next fill started that long before this one ended
+       "gap_fill_end_to_next_fill_start": stat(gaps),
+       "fills_overlapping_the_previous_fill": sum(g < 0 for g in gaps),
+       "walk_start_minus_its_fill_end": stat([(p["walk"][0] - p["fill"][1]) * 1e3 for p in per_step if p["walk"]]),
+       "per_step": per_step}
+json.dump(out, open(sys.argv[2], "w"), indent=1)
+print(json.dumps({a: b for a, b in out.items() if a != "per_step"}, indent=1))
