@@ -34,7 +34,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
 #include <string>
 #include <vector>
 
@@ -42,6 +41,7 @@
 #include "ta_context.h"
 #include "ta_device.h"
 #include "ta_host_batch.h"
+#include "ta_plan_driver.h"
 #include "ta_planner.h"
 #include "ta_packed.h"
 
@@ -1091,141 +1091,44 @@ hipError_t launch_affine_traceback(int mode, const AffArgs& a, hipStream_t s) {
 
 // ---------------------------------------------------------------------------
 // Host driver (the planning is ta_planner.cpp build_affine_plan).
-struct ta_affine_plan {
+struct TA_PLAN_LOCAL ta_affine_plan : ta::AffineArrays {  // the opaque plan, as the shared driver takes it (ta_plan_driver.h)
     ta_context* ctx = nullptr;
     ta::AffinePlan h;
     void* own_block = nullptr;  // device arrays of a plan made by ta_affine_plan_create (one allocation)
-    uint32_t *d_qlen = nullptr, *d_tlen = nullptr, *d_order = nullptr, *d_goal_i = nullptr, *d_goal_j = nullptr;
-    uint32_t *d_singles = nullptr, *d_duals = nullptr;
-    uint32_t* d_fb = nullptr;  // hand-back list [2 * couples], then one counter per chunk
-    uint64_t *d_ptr_off = nullptr, *d_bnd_off = nullptr, *d_slot_off = nullptr;
-    uint32_t *d_err = nullptr, *d_tickets = nullptr;  // packed fill: poll error word, one ticket counter per chunk
-    void* d_pout = nullptr;                           // PassOut[2] per (pass, couple) of one chunk
-    uint32_t* d_stask_off = nullptr;  // pipelined int32 fill: per single, its first task
-    uint64_t* d_stasks = nullptr;     // ... its tasks in ticket order
-    void* d_spout = nullptr;          // ... PassOut per task
+    static int exec_chunk(ta_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace);
+    // (int32-only plans without pipelined passes poll nothing)
+    uint32_t* err_word() const { return h.duals.empty() && h.single_tasks.empty() ? nullptr : d_err; }
+    static const char* err_message(uint32_t) {
+        return "affine fill: a pass hand-off poll timed out; results of this plan are invalid";
+    }
+};
+
+// ... as ta_align_batch_affine runs it: the same plan, its error said of the batch
+struct TA_PLAN_LOCAL AffineBatchPlan : ta_affine_plan {
+    static const char* err_message(uint32_t) {
+        return "affine fill: a pass hand-off poll timed out; results of this batch are invalid";
+    }
 };
 
 namespace {
 
 using ta_host::fail;
 
-struct AffOffs {
-    uint64_t qlen, tlen, order, singles, duals, stask_off, stasks, ptr_off, bnd_off, slot_off, err, tickets;  // uploaded
-    uint64_t goal_i, goal_j, fb, pout, spout;                                                               // device-only
-};
-
-// PassOut[2] per (pass, couple) of the largest chunk (24-byte PassOut)
-uint64_t aff_pout_bytes(const ta::AffinePlan& h) {
-    uint64_t n = 0;
-    for (const auto& ch : h.chunks) n = std::max<uint64_t>(n, 2ull * ch.dcount * ch.dpasses);
-    return n * 24ull;
-}
-
-template <class T>
-uint64_t avbytes(const std::vector<T>& v) {
-    return v.size() * sizeof(T);
-}
-
-AffOffs aff_layout(const ta::AffinePlan& h, ta::BlockLayout& L) {
-    AffOffs o{};
-    o.qlen = L.add(avbytes(h.qlen));
-    o.tlen = L.add(avbytes(h.tlen));
-    o.order = L.add(avbytes(h.order));
-    o.singles = L.add(avbytes(h.singles));
-    o.duals = L.add(avbytes(h.duals));
-    o.stask_off = L.add(avbytes(h.single_task_off));
-    o.stasks = L.add(avbytes(h.single_tasks));
-    o.ptr_off = L.add(avbytes(h.ptr_off));
-    o.bnd_off = L.add(avbytes(h.bnd_off));
-    o.slot_off = L.add(avbytes(h.slot_off));
-    o.err = L.add(4);
-    o.tickets = L.add(8ull * h.chunks.size());  // per chunk: packed, then pipelined int32
-    return o;
-}
-
-void aff_layout_scratch(const ta::AffinePlan& h, ta::BlockLayout& L, AffOffs& o) {
-    o.goal_i = L.add(4ull * h.n_pairs);
-    o.goal_j = L.add(4ull * h.n_pairs);
-    o.fb = L.add(4ull * (h.duals.size() + h.chunks.size()));
-    o.pout = L.add(aff_pout_bytes(h));
-    o.spout = L.add(h.single_tasks.size() * 24ull);
-}
-
-void aff_pack(const ta::AffinePlan& h, const AffOffs& o, uint8_t* base) {
-    auto put = [&](uint64_t at, const auto& v) {
-        if (!v.empty()) std::memcpy(base + at, v.data(), avbytes(v));
-    };
-    put(o.qlen, h.qlen);
-    put(o.tlen, h.tlen);
-    put(o.order, h.order);
-    put(o.singles, h.singles);
-    put(o.duals, h.duals);
-    put(o.stask_off, h.single_task_off);
-    put(o.stasks, h.single_tasks);
-    put(o.ptr_off, h.ptr_off);
-    put(o.bnd_off, h.bnd_off);
-    put(o.slot_off, h.slot_off);
-    std::memset(base + o.err, 0, 4);
-    std::memset(base + o.tickets, 0, 8ull * h.chunks.size());
-}
-
-void aff_bind(ta_affine_plan* pl, uint8_t* d, const AffOffs& o) {
-    auto u32 = [&](uint64_t at) { return reinterpret_cast<uint32_t*>(d + at); };
-    auto u64 = [&](uint64_t at) { return reinterpret_cast<uint64_t*>(d + at); };
-    pl->d_qlen = u32(o.qlen);
-    pl->d_tlen = u32(o.tlen);
-    pl->d_order = u32(o.order);
-    pl->d_singles = u32(o.singles);
-    pl->d_duals = u32(o.duals);
-    pl->d_ptr_off = u64(o.ptr_off);
-    pl->d_bnd_off = u64(o.bnd_off);
-    pl->d_slot_off = u64(o.slot_off);
-    pl->d_goal_i = u32(o.goal_i);
-    pl->d_goal_j = u32(o.goal_j);
-    pl->d_fb = u32(o.fb);
-    pl->d_err = u32(o.err);
-    pl->d_tickets = u32(o.tickets);
-    pl->d_pout = d + o.pout;
-    pl->d_stask_off = u32(o.stask_off);
-    pl->d_stasks = u64(o.stasks);
-    pl->d_spout = d + o.spout;
-}
-
-// the oracle's range (oracle_affine_in_range): every |value| < 2^26
-bool affine_in_range(uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, int match, int mismatch,
-                     int gap_open, int gap_extend) {
-    uint64_t maxn = 0, maxm = 0;
-    for (uint32_t p = 0; p < n_pairs; ++p) {
-        maxn = std::max<uint64_t>(maxn, qlen[p]);
-        maxm = std::max<uint64_t>(maxm, tlen[p]);
-    }
-    const long long pm = std::max({std::llabs(match), std::llabs(mismatch),
-                                   std::llabs(gap_open) + std::llabs(gap_extend)});
-    return (long long)(maxn + maxm + 2) * pm < (1ll << 26);
-}
-
 int affine_check_args(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, int type,
                       int match, int mismatch, int gap_open, int gap_extend) {
     if (!ctx) return TA_ERR_ARG;
     if (n_pairs && (!qlen || !tlen)) return fail(ctx, TA_ERR_ARG, "null argument");
-    if (type != TA_GLOBAL && type != TA_LOCAL && type != TA_SEMI_GLOBAL)
-        return fail(ctx, TA_ERR_BAD_TYPE, ta_status_string(TA_ERR_BAD_TYPE));
-    if (!affine_in_range(n_pairs, qlen, tlen, match, mismatch, gap_open, gap_extend))
+    if (!ta_host::valid_type(type)) return fail(ctx, TA_ERR_BAD_TYPE, ta_status_string(TA_ERR_BAD_TYPE));
+    const long long max_step = std::max({std::llabs(match), std::llabs(mismatch),
+                                         std::llabs(gap_open) + std::llabs(gap_extend)});
+    if (!ta_host::in_range(n_pairs, qlen, tlen, max_step))
         return fail(ctx, TA_ERR_RANGE, ta_status_string(TA_ERR_RANGE));
     return TA_OK;
 }
 
-int affine_check_io(ta_affine_plan* pl, const ta_device_io* io) {
-    if (!pl || !io) return TA_ERR_ARG;
-    if (pl->h.n_pairs && (!io->query_off || !io->target_off || !io->score || !io->target_begin))
-        return fail(pl->ctx, TA_ERR_ARG, "null device pointer");
-    if (pl->h.want_cigar && pl->h.n_pairs && (!io->cigar_slots || !io->cigar_start || !io->cigar_len))
-        return fail(pl->ctx, TA_ERR_ARG, "null cigar device pointer");
-    return TA_OK;
-}
+}  // namespace
 
-int affine_exec_chunk(ta_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace) {
+int ta_affine_plan::exec_chunk(ta_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace) {
     ta_context* ctx = pl->ctx;
     const ta::AffinePlan& h = pl->h;
     if (int r = ta_host::grow(ctx, ctx->ws_ptrs, h.ws_ptr_entries * sizeof(uint2))) return r;
@@ -1312,49 +1215,9 @@ int affine_exec_chunk(ta_affine_plan* pl, const ta_device_io* io, hipStream_t s,
     return TA_OK;
 }
 
-int affine_exec(ta_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t chunk, bool fill, bool trace) {
-    ta_context* ctx = pl->ctx;
-    TA_HIP(ctx, hipSetDevice(ctx->device));
-    if (int r = ta_host::stream_enter(ctx, s)) return r;
-    const uint32_t c0 = chunk == UINT32_MAX ? 0 : chunk;
-    const uint32_t c1 = chunk == UINT32_MAX ? (uint32_t)pl->h.chunks.size() : chunk + 1;
-    for (uint32_t c = c0; c < c1; ++c)
-        if (int r = affine_exec_chunk(pl, io, s, c, fill, trace)) return r;
-    return ta_host::stream_leave(ctx, s);
-}
-
-struct AffineHostPlan final : ta_host::HostPlan {
-    ta_affine_plan* pl;
-    AffOffs o{};
-    explicit AffineHostPlan(ta_affine_plan* p) : pl(p) {}
-    void layout(ta::BlockLayout& L) override { o = aff_layout(pl->h, L); }
-    void pack(uint8_t* base) override { aff_pack(pl->h, o, base); }
-    void layout_device_only(ta::BlockLayout& L) override { aff_layout_scratch(pl->h, L, o); }
-    void bind(uint8_t* dev) override { aff_bind(pl, dev, o); }
-    int execute(const ta_device_io* io, hipStream_t s) override {
-        return affine_exec(pl, io, s, UINT32_MAX, true, true);
-    }
-    uint64_t slots_bytes() const override { return pl->h.slots_bytes; }
-    uint64_t err_offset() const override {
-        return pl->h.duals.empty() && pl->h.single_tasks.empty() ? UINT64_MAX : o.err;
-    }
-    const char* err_message(uint32_t) const override {
-        return "affine fill: a pass hand-off poll timed out; results of this batch are invalid";
-    }
-};
-
-}  // namespace
-
 extern "C" {
 
-void ta_affine_plan_destroy(ta_affine_plan* pl) {
-    if (!pl) return;
-    if (pl->own_block) {
-        (void)hipSetDevice(pl->ctx->device);
-        (void)hipFree(pl->own_block);
-    }
-    delete pl;
-}
+void ta_affine_plan_destroy(ta_affine_plan* pl) { ta_host::plan_destroy(pl); }
 
 int ta_affine_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, int type,
                           int match, int mismatch, int gap_open, int gap_extend, int want_cigar, uint64_t budget,
@@ -1367,36 +1230,12 @@ int ta_affine_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qle
     pl->ctx = ctx;
     ta::build_affine_plan(pl->h, n_pairs, qlen, tlen, type, match, mismatch, gap_open, gap_extend, want_cigar != 0,
                           budget ? budget : ta_host::default_budget(ctx), flags, 4 * ctx->cu_count);
-    ta::BlockLayout L;
-    AffOffs o = aff_layout(pl->h, L);
-    const uint64_t upload = L.bytes;
-    aff_layout_scratch(pl->h, L, o);
-    std::vector<uint8_t> host(upload);
-    aff_pack(pl->h, o, host.data());
-    hipError_t e = hipMalloc(&pl->own_block, std::max<uint64_t>(L.bytes, 256));
-    if (e == hipSuccess) e = hipMemcpy(pl->own_block, host.data(), upload, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        ta_affine_plan_destroy(pl);
-        return fail(ctx, TA_ERR_DEVICE, std::string("ta_affine_plan_create: ") + hipGetErrorString(e));
-    }
-    aff_bind(pl, static_cast<uint8_t*>(pl->own_block), o);
-    *out = pl;
-    return TA_OK;
+    return ta_host::plan_create_block(pl, "ta_affine_plan_create: ", out);
 }
 
 uint64_t ta_affine_plan_cigar_slots_bytes(const ta_affine_plan* pl) { return pl ? pl->h.slots_bytes : 0; }
 
-int ta_affine_plan_check(ta_affine_plan* pl) {
-    if (!pl) return TA_ERR_ARG;
-    if (pl->h.duals.empty() && pl->h.single_tasks.empty()) return TA_OK;
-    uint32_t err = 0;
-    TA_HIP(pl->ctx, hipSetDevice(pl->ctx->device));
-    TA_HIP(pl->ctx, hipMemcpy(&err, pl->d_err, 4, hipMemcpyDeviceToHost));
-    if (!err) return TA_OK;
-    TA_HIP(pl->ctx, hipMemset(pl->d_err, 0, 4));
-    return fail(pl->ctx, TA_ERR_DEVICE,
-                "affine fill: a pass hand-off poll timed out; results of this plan are invalid");
-}
+int ta_affine_plan_check(ta_affine_plan* pl) { return ta_host::plan_check(pl); }
 uint64_t ta_affine_plan_workspace_bytes(const ta_affine_plan* pl) {
     return pl ? pl->h.ws_ptr_entries * sizeof(uint2) + pl->h.ws_bnd_entries * sizeof(int2) : 0;
 }
@@ -1405,49 +1244,19 @@ ta_context* ta_affine_plan_context(const ta_affine_plan* pl) { return pl ? pl->c
 uint32_t ta_affine_plan_dual_pairs(const ta_affine_plan* pl) { return pl ? (uint32_t)pl->h.duals.size() : 0; }
 
 int ta_affine_plan_pair_chunks(const ta_affine_plan* pl, uint32_t* chunk_of_pair) {
-    if (!pl || !chunk_of_pair) return TA_ERR_ARG;
-    for (uint32_t c = 0; c < (uint32_t)pl->h.chunks.size(); ++c) {
-        const auto& ch = pl->h.chunks[c];
-        for (uint32_t k = ch.begin; k < ch.begin + ch.count; ++k) chunk_of_pair[pl->h.order[k]] = c;
-    }
-    return TA_OK;
+    return ta_host::plan_pair_chunks(pl, chunk_of_pair);
 }
-
 int ta_affine_plan_execute(ta_affine_plan* pl, const ta_device_io* io, void* stream) {
-    if (int r = affine_check_io(pl, io)) return r;
-    std::lock_guard<std::mutex> lock(pl->ctx->mu);
-    return affine_exec(pl, io, (hipStream_t)stream, UINT32_MAX, true, true);
+    return ta_host::plan_execute(pl, io, stream);
 }
-
-int ta_affine_plan_annotate(ta_affine_plan* pl, const ta_device_io* io, const ta_annotate_io* out, void* stream) {
-    if (!pl || !io || !out) return TA_ERR_ARG;
-    ta_context* ctx = pl->ctx;
-    if (!pl->h.want_cigar) return fail(ctx, TA_ERR_ARG, "annotate: the plan has no CIGARs");
-    if (out->eqx_slots && (!out->eqx_start || !out->eqx_len)) return fail(ctx, TA_ERR_ARG, "annotate: eqx_slots without eqx_start / eqx_len");
-    if (int r = affine_check_io(pl, io)) return r;
-    if (!pl->h.n_pairs) return TA_OK;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    TA_HIP(ctx, hipSetDevice(ctx->device));
-    ta::AnnotateArgs a{pl->h.n_pairs, pl->h.type, pl->d_qlen, pl->d_tlen, pl->d_goal_i, pl->d_goal_j, pl->d_slot_off,
-                       reinterpret_cast<const uint8_t*>(io->query_bytes), io->query_off,
-                       reinterpret_cast<const uint8_t*>(io->target_bytes), io->target_off, io->cigar_slots,
-                       io->cigar_start, io->cigar_len, out->info, out->eqx_slots, out->eqx_start, out->eqx_len};
-    TA_HIP(ctx, ta::launch_annotate(a, (hipStream_t)stream));
-    return TA_OK;
-}
-
 int ta_affine_plan_execute_fill(ta_affine_plan* pl, const ta_device_io* io, void* stream, uint32_t chunk) {
-    if (int r = affine_check_io(pl, io)) return r;
-    if (chunk >= pl->h.chunks.size()) return pl->h.n_pairs ? TA_ERR_ARG : TA_OK;
-    std::lock_guard<std::mutex> lock(pl->ctx->mu);
-    return affine_exec(pl, io, (hipStream_t)stream, chunk, true, false);
+    return ta_host::plan_execute_chunk(pl, io, stream, chunk, true);
 }
-
 int ta_affine_plan_execute_traceback(ta_affine_plan* pl, const ta_device_io* io, void* stream, uint32_t chunk) {
-    if (int r = affine_check_io(pl, io)) return r;
-    if (chunk >= pl->h.chunks.size()) return pl->h.n_pairs ? TA_ERR_ARG : TA_OK;
-    std::lock_guard<std::mutex> lock(pl->ctx->mu);
-    return affine_exec(pl, io, (hipStream_t)stream, chunk, false, true);
+    return ta_host::plan_execute_chunk(pl, io, stream, chunk, false);
+}
+int ta_affine_plan_annotate(ta_affine_plan* pl, const ta_device_io* io, const ta_annotate_io* out, void* stream) {
+    return ta_host::plan_annotate(pl, io, out, stream);
 }
 
 int ta_align_batch_affine(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
@@ -1463,13 +1272,12 @@ int ta_align_batch_affine(ta_context* ctx, uint32_t n_pairs, const char* qb, con
     if (int r = affine_check_args(ctx, n_pairs, qlen, tlen, type, match, mismatch, gap_open, gap_extend)) return r;
     std::lock_guard<std::mutex> lock(ctx->mu);
     TA_HIP(ctx, hipSetDevice(ctx->device));
-    ta_affine_plan pl;
+    AffineBatchPlan pl;
     pl.ctx = ctx;
     ta::build_affine_plan(pl.h, n_pairs, qlen, tlen, type, match, mismatch, gap_open, gap_extend, want_cigar != 0,
                           ta_host::batch_budget(ctx, n_pairs, qlen, tlen, want_cigar, sizeof(uint2)), 0,
                           4 * ctx->cu_count);
-    AffineHostPlan hp(&pl);
-    return ta_host::host_batch(ctx, hp, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
+    return ta_host::host_batch(ctx, pl, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
                                target_begin, arena, arena_bytes, cigar_off, cigar_len);
 }
 

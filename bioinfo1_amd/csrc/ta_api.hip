@@ -19,144 +19,40 @@
 #include "ta_host_batch.h"
 #include "ta_internal.h"
 #include "ta_pipeline_internal.h"
+#include "ta_plan_driver.h"
 #include "ta_planner.h"
 
 using ta_host::fail;
 
-struct ta_plan {
+// The opaque linear plan, as the shared driver takes it (ta_plan_driver.h).
+struct TA_PLAN_LOCAL ta_plan : ta::PlanArrays {  // device arrays: inside own_block, or inside ctx->blk for host-memory batches
     ta_context* ctx = nullptr;
-    ta::Plan h;               // host plan (ta_planner.h)
+    ta::Plan h;                 // host plan (ta_planner.h)
     void* own_block = nullptr;  // device arrays of a plan made by ta_plan_create (one allocation)
-    // device arrays (inside own_block, or inside ctx->blk for host-memory batches)
-    uint32_t *d_qlen = nullptr, *d_tlen = nullptr, *d_order = nullptr, *d_singles = nullptr, *d_duals = nullptr,
-             *d_flexes = nullptr;
-    uint64_t *d_ptr_off = nullptr, *d_bnd_off = nullptr, *d_slot_off = nullptr;
-    uint32_t *d_goal_i = nullptr, *d_goal_j = nullptr;
-    uint32_t* d_fb = nullptr;  // packed-fill hand-back: [n_dual_pairs] list, then one counter per chunk
-    uint32_t *d_flex_task_off = nullptr, *d_tickets = nullptr, *d_err = nullptr, *d_flex_tasks = nullptr;
-    void* d_pout = nullptr;  // PassOut[2] per flex task
-    void* d_dpout = nullptr;  // PassOut[2] per (pass, dual couple) of one multi-pass chunk
-    uint32_t* d_stask_off = nullptr;  // pipelined int32 fill: per single, its first task
-    uint64_t* d_stasks = nullptr;     // ... its tasks in ticket order
-    void* d_spout = nullptr;          // ... PassOut per task
-    uint8_t* d_pflag = nullptr;       // blk plans: per pair, handed back by the dual fill (band walk skips it)
+    static int exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace);
+    // (int32-only plans without pipelined passes have no kernel that reports)
+    uint32_t* err_word() const { return h.flexes.empty() && h.duals.empty() && h.single_tasks.empty() ? nullptr : d_err; }
+    static const char* err_message(uint32_t err) {
+        if (err & ta::kErrWalkCap) return "traceback: a band walk reached its event cap with cost left; results of this plan are invalid";
+        return "packed fill: a pass hand-off poll timed out; results of this plan are invalid";
+    }
 };
 
 namespace {
 
-bool valid_type(int t) { return t == TA_GLOBAL || t == TA_LOCAL || t == TA_SEMI_GLOBAL; }
-
-// Offsets of a linear plan's arrays in its device block.  Everything before
-// `upload_end` is copied from the host (the error word and ticket counters
-// as zeros); goal cells, the hand-back list and the pass results are device-only.
-struct PlanOffs {
-    uint64_t qlen, tlen, order, singles, duals, flexes, task_off, tasks, stask_off, stasks, ptr_off, bnd_off, slot_off,
-        err, tickets;
-    uint64_t goal_i, goal_j, fb, pout, dpout, spout, pflag;
-};
-
-// PassOut[2] (24 bytes each) per (pass, couple) of the largest multi-pass dual chunk
-uint64_t dual_pout_bytes(const ta::Plan& h) {
-    uint64_t n = 0;
-    for (const auto& ch : h.chunks)
-        if (ch.dpasses > 1) n = std::max<uint64_t>(n, 2ull * ch.dcount * ch.dpasses);
-    return n * 24ull;
-}
-
-template <class T>
-uint64_t vbytes(const std::vector<T>& v) {
-    return v.size() * sizeof(T);
-}
-
-PlanOffs layout_uploaded(const ta::Plan& h, ta::BlockLayout& L) {
-    PlanOffs o{};
-    o.qlen = L.add(vbytes(h.qlen));
-    o.tlen = L.add(vbytes(h.tlen));
-    o.order = L.add(vbytes(h.order));
-    o.singles = L.add(vbytes(h.singles));
-    o.duals = L.add(vbytes(h.duals));
-    o.flexes = L.add(vbytes(h.flexes));
-    o.task_off = L.add(vbytes(h.flex_task_off));
-    o.tasks = L.add(vbytes(h.flex_tasks));
-    o.stask_off = L.add(vbytes(h.single_task_off));
-    o.stasks = L.add(vbytes(h.single_tasks));
-    o.ptr_off = L.add(vbytes(h.ptr_off));
-    o.bnd_off = L.add(vbytes(h.bnd_off));
-    o.slot_off = L.add(vbytes(h.slot_off));
-    o.err = L.add(4);
-    o.tickets = L.add(12ull * h.chunks.size());  // per chunk: flex, then dual, then pipelined int32
-    return o;
-}
-
-void layout_scratch(const ta::Plan& h, ta::BlockLayout& L, PlanOffs& o) {
-    o.goal_i = L.add(4ull * h.n_pairs);
-    o.goal_j = L.add(4ull * h.n_pairs);
-    o.fb = L.add(4ull * (h.n_dual_pairs + h.chunks.size()));
-    o.pout = L.add(h.flexes.empty() ? 0 : h.flex_task_off.back() * 48ull + 16);
-    o.dpout = L.add(dual_pout_bytes(h));
-    o.spout = L.add(h.single_tasks.size() * 24ull);
-    o.pflag = L.add(h.blk ? h.n_pairs : 0);
-}
-
-void pack(const ta::Plan& h, const PlanOffs& o, uint8_t* base) {
-    auto put = [&](uint64_t at, const auto& v) {
-        if (!v.empty()) std::memcpy(base + at, v.data(), vbytes(v));
-    };
-    put(o.qlen, h.qlen);
-    put(o.tlen, h.tlen);
-    put(o.order, h.order);
-    put(o.singles, h.singles);
-    put(o.duals, h.duals);
-    put(o.flexes, h.flexes);
-    put(o.task_off, h.flex_task_off);
-    put(o.tasks, h.flex_tasks);
-    put(o.stask_off, h.single_task_off);
-    put(o.stasks, h.single_tasks);
-    put(o.ptr_off, h.ptr_off);
-    put(o.bnd_off, h.bnd_off);
-    put(o.slot_off, h.slot_off);
-    std::memset(base + o.err, 0, 4);
-    std::memset(base + o.tickets, 0, 12ull * h.chunks.size());
-}
-
-void bind(ta_plan* pl, uint8_t* d, const PlanOffs& o) {
-    auto u32 = [&](uint64_t at) { return reinterpret_cast<uint32_t*>(d + at); };
-    auto u64 = [&](uint64_t at) { return reinterpret_cast<uint64_t*>(d + at); };
-    pl->d_qlen = u32(o.qlen);
-    pl->d_tlen = u32(o.tlen);
-    pl->d_order = u32(o.order);
-    pl->d_singles = u32(o.singles);
-    pl->d_duals = u32(o.duals);
-    pl->d_flexes = u32(o.flexes);
-    pl->d_flex_task_off = u32(o.task_off);
-    pl->d_flex_tasks = u32(o.tasks);
-    pl->d_ptr_off = u64(o.ptr_off);
-    pl->d_bnd_off = u64(o.bnd_off);
-    pl->d_slot_off = u64(o.slot_off);
-    pl->d_err = u32(o.err);
-    pl->d_tickets = u32(o.tickets);
-    pl->d_goal_i = u32(o.goal_i);
-    pl->d_goal_j = u32(o.goal_j);
-    pl->d_fb = u32(o.fb);
-    pl->d_pout = d + o.pout;
-    pl->d_dpout = d + o.dpout;
-    pl->d_stask_off = u32(o.stask_off);
-    pl->d_stasks = u64(o.stasks);
-    pl->d_spout = d + o.spout;
-    pl->d_pflag = d + o.pflag;
-}
-
 int check_args(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, int type) {
     if (!ctx) return TA_ERR_ARG;
     if (n_pairs && (!qlen || !tlen)) return fail(ctx, TA_ERR_ARG, "null argument");
-    if (!valid_type(type)) return fail(ctx, TA_ERR_BAD_TYPE, ta_status_string(TA_ERR_BAD_TYPE));
+    if (!ta_host::valid_type(type)) return fail(ctx, TA_ERR_BAD_TYPE, ta_status_string(TA_ERR_BAD_TYPE));
     return TA_OK;
 }
+
+}  // namespace
 
 // Launches of one chunk: the fill kernels (int32 singles, equal-shape dual
 // couples, rebased flex couples, and the int32 fill of the couples the packed
 // kernels hand back), then the traceback kernel.
-int exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace) {
+int ta_plan::exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace) {
     const ta::Plan& h = pl->h;
     const auto& ch = h.chunks[c];
     ta_context* ctx = pl->ctx;
@@ -335,51 +231,6 @@ int exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, b
     return TA_OK;
 }
 
-int check_io(ta_plan* pl, const ta_device_io* io) {
-    if (!pl || !io) return TA_ERR_ARG;
-    if (pl->h.n_pairs && (!io->query_off || !io->target_off || !io->score || !io->target_begin))
-        return fail(pl->ctx, TA_ERR_ARG, "null device pointer");
-    if (pl->h.want_cigar && pl->h.n_pairs && (!io->cigar_slots || !io->cigar_start || !io->cigar_len))
-        return fail(pl->ctx, TA_ERR_ARG, "null cigar device pointer");
-    return TA_OK;
-}
-
-// chunk == UINT32_MAX: every chunk
-int exec(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t chunk, bool fill, bool trace) {
-    ta_context* ctx = pl->ctx;
-    TA_HIP(ctx, hipSetDevice(ctx->device));
-    if (int r = ta_host::stream_enter(ctx, s)) return r;
-    const uint32_t c0 = chunk == UINT32_MAX ? 0 : chunk;
-    const uint32_t c1 = chunk == UINT32_MAX ? (uint32_t)pl->h.chunks.size() : chunk + 1;
-    for (uint32_t c = c0; c < c1; ++c)
-        if (int r = exec_chunk(pl, io, s, c, fill, trace)) return r;
-    return ta_host::stream_leave(ctx, s);
-}
-
-// The linear plan as the host-memory batch driver sees it (ta_host_batch.h).
-const char* plan_err_message(uint32_t err) {
-    if (err & ta::kErrWalkCap) return "traceback: a band walk reached its event cap with cost left; results of this plan are invalid";
-    return "packed fill: a pass hand-off poll timed out; results of this plan are invalid";
-}
-
-struct LinearHostPlan final : ta_host::HostPlan {
-    ta_plan* pl;
-    PlanOffs o{};
-    explicit LinearHostPlan(ta_plan* p) : pl(p) {}
-    void layout(ta::BlockLayout& L) override { o = layout_uploaded(pl->h, L); }
-    void pack(uint8_t* base) override { ::pack(pl->h, o, base); }
-    void layout_device_only(ta::BlockLayout& L) override { layout_scratch(pl->h, L, o); }
-    void bind(uint8_t* dev) override { ::bind(pl, dev, o); }
-    int execute(const ta_device_io* io, hipStream_t s) override { return exec(pl, io, s, UINT32_MAX, true, true); }
-    uint64_t slots_bytes() const override { return pl->h.slots_bytes; }
-    uint64_t err_offset() const override {
-        return pl->h.flexes.empty() && pl->h.duals.empty() && pl->h.single_tasks.empty() ? UINT64_MAX : o.err;
-    }
-    const char* err_message(uint32_t err) const override { return plan_err_message(err); }
-};
-
-}  // namespace
-
 extern "C" {
 
 const char* ta_status_string(int status) {
@@ -462,14 +313,7 @@ void ta_context_destroy(ta_context* ctx) {
     delete ctx;
 }
 
-void ta_plan_destroy(ta_plan* pl) {
-    if (!pl) return;
-    if (pl->own_block) {
-        (void)hipSetDevice(pl->ctx->device);
-        (void)hipFree(pl->own_block);
-    }
-    delete pl;
-}
+void ta_plan_destroy(ta_plan* pl) { ta_host::plan_destroy(pl); }
 
 int ta_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, int type,
                    int match, int mismatch, int gap, int want_cigar, uint64_t budget, uint32_t flags, ta_plan** out) {
@@ -481,22 +325,7 @@ int ta_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, cons
     pl->ctx = ctx;
     ta::build_plan(pl->h, n_pairs, qlen, tlen, type, match, mismatch, gap, want_cigar != 0,
                    budget ? budget : ta_host::default_budget(ctx), flags, 4 * ctx->cu_count);
-    // all per-pair arrays in one device allocation, uploaded in one copy
-    ta::BlockLayout L;
-    PlanOffs o = layout_uploaded(pl->h, L);
-    const uint64_t upload = L.bytes;
-    layout_scratch(pl->h, L, o);
-    std::vector<uint8_t> host(upload);
-    pack(pl->h, o, host.data());
-    hipError_t e = hipMalloc(&pl->own_block, std::max<uint64_t>(L.bytes, 256));
-    if (e == hipSuccess) e = hipMemcpy(pl->own_block, host.data(), upload, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        ta_plan_destroy(pl);
-        return fail(ctx, TA_ERR_DEVICE, std::string("ta_plan_create: ") + hipGetErrorString(e));
-    }
-    bind(pl, static_cast<uint8_t*>(pl->own_block), o);
-    *out = pl;
-    return TA_OK;
+    return ta_host::plan_create_block(pl, "ta_plan_create: ", out);
 }
 
 uint64_t ta_plan_cigar_slots_bytes(const ta_plan* pl) { return pl ? pl->h.slots_bytes : 0; }
@@ -522,61 +351,17 @@ int ta_plan_walk(const ta_plan* pl) {
     return pl->h.walk_group | (pl->h.blk ? 0x100 : 0) | (pl->h.ck ? 0x200 : 0);
 }
 
-int ta_plan_pair_chunks(const ta_plan* pl, uint32_t* chunk_of_pair) {
-    if (!pl || !chunk_of_pair) return TA_ERR_ARG;
-    for (uint32_t c = 0; c < (uint32_t)pl->h.chunks.size(); ++c) {
-        const auto& ch = pl->h.chunks[c];
-        for (uint32_t k = ch.begin; k < ch.begin + ch.count; ++k) chunk_of_pair[pl->h.order[k]] = c;
-    }
-    return TA_OK;
-}
-
-int ta_plan_execute(ta_plan* pl, const ta_device_io* io, void* stream) {
-    if (int r = check_io(pl, io)) return r;
-    std::lock_guard<std::mutex> lock(pl->ctx->mu);
-    return exec(pl, io, (hipStream_t)stream, UINT32_MAX, true, true);
-}
-
+int ta_plan_pair_chunks(const ta_plan* pl, uint32_t* chunk_of_pair) { return ta_host::plan_pair_chunks(pl, chunk_of_pair); }
+int ta_plan_execute(ta_plan* pl, const ta_device_io* io, void* stream) { return ta_host::plan_execute(pl, io, stream); }
 int ta_plan_execute_fill(ta_plan* pl, const ta_device_io* io, void* stream, uint32_t chunk) {
-    if (int r = check_io(pl, io)) return r;
-    if (chunk >= pl->h.chunks.size()) return pl->h.n_pairs ? TA_ERR_ARG : TA_OK;
-    std::lock_guard<std::mutex> lock(pl->ctx->mu);
-    return exec(pl, io, (hipStream_t)stream, chunk, true, false);
+    return ta_host::plan_execute_chunk(pl, io, stream, chunk, true);
 }
-
 int ta_plan_execute_traceback(ta_plan* pl, const ta_device_io* io, void* stream, uint32_t chunk) {
-    if (int r = check_io(pl, io)) return r;
-    if (chunk >= pl->h.chunks.size()) return pl->h.n_pairs ? TA_ERR_ARG : TA_OK;
-    std::lock_guard<std::mutex> lock(pl->ctx->mu);
-    return exec(pl, io, (hipStream_t)stream, chunk, false, true);
+    return ta_host::plan_execute_chunk(pl, io, stream, chunk, false);
 }
-
-int ta_plan_check(ta_plan* pl) {
-    if (!pl) return TA_ERR_ARG;
-    if (pl->h.flexes.empty() && pl->h.duals.empty() && pl->h.single_tasks.empty()) return TA_OK;
-    uint32_t err = 0;
-    TA_HIP(pl->ctx, hipSetDevice(pl->ctx->device));
-    TA_HIP(pl->ctx, hipMemcpy(&err, pl->d_err, 4, hipMemcpyDeviceToHost));
-    if (!err) return TA_OK;
-    TA_HIP(pl->ctx, hipMemset(pl->d_err, 0, 4));
-    return fail(pl->ctx, TA_ERR_DEVICE, plan_err_message(err));
-}
-
+int ta_plan_check(ta_plan* pl) { return ta_host::plan_check(pl); }
 int ta_plan_annotate(ta_plan* pl, const ta_device_io* io, const ta_annotate_io* out, void* stream) {
-    if (!pl || !io || !out) return TA_ERR_ARG;
-    ta_context* ctx = pl->ctx;
-    if (!pl->h.want_cigar) return fail(ctx, TA_ERR_ARG, "annotate: the plan has no CIGARs");
-    if (out->eqx_slots && (!out->eqx_start || !out->eqx_len)) return fail(ctx, TA_ERR_ARG, "annotate: eqx_slots without eqx_start / eqx_len");
-    if (int r = check_io(pl, io)) return r;
-    if (!pl->h.n_pairs) return TA_OK;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    TA_HIP(ctx, hipSetDevice(ctx->device));
-    ta::AnnotateArgs a{pl->h.n_pairs, pl->h.type, pl->d_qlen, pl->d_tlen, pl->d_goal_i, pl->d_goal_j, pl->d_slot_off,
-                       reinterpret_cast<const uint8_t*>(io->query_bytes), io->query_off,
-                       reinterpret_cast<const uint8_t*>(io->target_bytes), io->target_off, io->cigar_slots,
-                       io->cigar_start, io->cigar_len, out->info, out->eqx_slots, out->eqx_start, out->eqx_len};
-    TA_HIP(ctx, ta::launch_annotate(a, (hipStream_t)stream));
-    return TA_OK;
+    return ta_host::plan_annotate(pl, io, out, stream);
 }
 
 int ta_compact_cigars(ta_context* ctx, uint32_t n_pairs, const char* cigar_slots, const uint64_t* cigar_start,
@@ -614,8 +399,7 @@ int ta_align_batch_flags(ta_context* ctx, uint32_t n_pairs, const char* qb, cons
     pl.ctx = ctx;
     ta::build_plan(pl.h, n_pairs, qlen, tlen, type, match, mismatch, gap, want_cigar != 0,
                    ta_host::batch_budget(ctx, n_pairs, qlen, tlen, want_cigar, 4), flags, 4 * ctx->cu_count);
-    LinearHostPlan hp(&pl);
-    return ta_host::host_batch(ctx, hp, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
+    return ta_host::host_batch(ctx, pl, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
                                target_begin, arena, arena_bytes, cigar_off, cigar_len);
 }
 

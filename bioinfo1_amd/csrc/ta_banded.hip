@@ -32,7 +32,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
 #include <string>
 #include <vector>
 
@@ -40,6 +39,7 @@
 #include "ta_context.h"
 #include "ta_device.h"
 #include "ta_host_batch.h"
+#include "ta_plan_driver.h"
 #include "ta_planner.h"
 
 namespace ta {
@@ -500,177 +500,37 @@ hipError_t launch_banded_traceback(int mode, const BandArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------
-// The plan: pairs by descending swept cells (the long ones start first), chunks
-// closed when the next pair's codes would pass the budget.
-struct BandPlan {
-    uint32_t n_pairs = 0;
-    int type = 0, match = 0, mismatch = 0, gap = 0;
-    bool want_cigar = false;
-    std::vector<uint32_t> qlen, tlen, band, order;
-    std::vector<uint64_t> ptr_off, bnd_off, slot_off;
-    struct Chunk {
-        uint32_t begin, count;
-        uint64_t ptr_dwords, bnd_words;
-    };
-    std::vector<Chunk> chunks;
-    uint64_t slots_bytes = 0, ws_ptr_dwords = 0, ws_bnd_words = 0;
-    uint64_t band_cells = 0, swept_cells = 0;
-};
-
-void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
-                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget) {
-    pl = BandPlan{};
-    pl.n_pairs = n_pairs;
-    pl.type = type;
-    pl.match = match;
-    pl.mismatch = mismatch;
-    pl.gap = gap;
-    pl.want_cigar = want_cigar;
-    pl.qlen.assign(qlen, qlen + n_pairs);
-    pl.tlen.assign(tlen, tlen + n_pairs);
-    pl.band.resize(n_pairs);
-    std::vector<uint64_t> swept(n_pairs);
-    pl.slot_off.resize(n_pairs);
-    for (uint32_t p = 0; p < n_pairs; ++p) {
-        pl.band[p] = band_clamp(qlen[p], tlen[p], band[p]);
-        swept[p] = band_swept_cells(qlen[p], tlen[p], pl.band[p]);
-        pl.swept_cells += swept[p];
-        pl.band_cells += band_cells(qlen[p], tlen[p], pl.band[p]);
-        pl.slot_off[p] = pl.slots_bytes;
-        pl.slots_bytes += cigar_slot_bytes(qlen[p], tlen[p]);
-    }
-    pl.order.resize(n_pairs);
-    std::iota(pl.order.begin(), pl.order.end(), 0u);
-    std::stable_sort(pl.order.begin(), pl.order.end(), [&](uint32_t x, uint32_t y) { return swept[x] > swept[y]; });
-    const uint64_t budget_dw = std::max<uint64_t>(budget / 4, 1);
-    pl.ptr_off.assign(n_pairs, 0);
-    pl.bnd_off.assign(n_pairs, 0);
-    BandPlan::Chunk c{0, 0, 0, 0};
-    for (uint32_t k = 0; k < n_pairs; ++k) {
-        const uint32_t p = pl.order[k];
-        const uint64_t codes = want_cigar ? band_ptr_dwords(qlen[p], tlen[p], pl.band[p]) : 0;
-        if (c.count && c.ptr_dwords + codes > budget_dw) {
-            pl.chunks.push_back(c);
-            c = {k, 0, 0, 0};
-        }
-        pl.ptr_off[p] = c.ptr_dwords;
-        pl.bnd_off[p] = c.bnd_words;
-        c.ptr_dwords += codes;
-        c.bnd_words += bnd_words(qlen[p], tlen[p]);
-        ++c.count;
-    }
-    if (c.count) pl.chunks.push_back(c);
-    for (const auto& ch : pl.chunks) {
-        pl.ws_ptr_dwords = std::max(pl.ws_ptr_dwords, ch.ptr_dwords);
-        pl.ws_bnd_words = std::max(pl.ws_bnd_words, ch.bnd_words);
-    }
-}
-
 }  // namespace
 }  // namespace ta
 
 // ---------------------------------------------------------------------------
-// Host driver.
-struct ta_banded_plan {
+// Host driver (the planning is ta_planner.cpp build_band_plan).
+struct TA_PLAN_LOCAL ta_banded_plan : ta::BandArrays {  // the opaque plan, as the shared driver takes it (ta_plan_driver.h)
     ta_context* ctx = nullptr;
     ta::BandPlan h;
     void* own_block = nullptr;  // device arrays of a plan made by ta_banded_plan_create (one allocation)
-    uint32_t *d_qlen = nullptr, *d_tlen = nullptr, *d_band = nullptr, *d_order = nullptr;
-    uint32_t *d_goal_i = nullptr, *d_goal_j = nullptr;
-    uint64_t *d_ptr_off = nullptr, *d_bnd_off = nullptr, *d_slot_off = nullptr;
+    static int exec_chunk(ta_banded_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace);
+    uint32_t* err_word() const { return nullptr; }  // (no polls: one wave sweeps a pair's passes)
+    static const char* err_message(uint32_t) { return ""; }
 };
 
 namespace {
 
 using ta_host::fail;
 
-struct BandOffs {
-    uint64_t qlen, tlen, band, order, ptr_off, bnd_off, slot_off;  // uploaded
-    uint64_t goal_i, goal_j;                                       // device-only
-};
-
-template <class T>
-uint64_t bvbytes(const std::vector<T>& v) {
-    return v.size() * sizeof(T);
-}
-
-BandOffs band_layout(const ta::BandPlan& h, ta::BlockLayout& L) {
-    BandOffs o{};
-    o.qlen = L.add(bvbytes(h.qlen));
-    o.tlen = L.add(bvbytes(h.tlen));
-    o.band = L.add(bvbytes(h.band));
-    o.order = L.add(bvbytes(h.order));
-    o.ptr_off = L.add(bvbytes(h.ptr_off));
-    o.bnd_off = L.add(bvbytes(h.bnd_off));
-    o.slot_off = L.add(bvbytes(h.slot_off));
-    return o;
-}
-
-void band_layout_scratch(const ta::BandPlan& h, ta::BlockLayout& L, BandOffs& o) {
-    o.goal_i = L.add(4ull * h.n_pairs);
-    o.goal_j = L.add(4ull * h.n_pairs);
-}
-
-void band_pack(const ta::BandPlan& h, const BandOffs& o, uint8_t* base) {
-    auto put = [&](uint64_t at, const auto& v) {
-        if (!v.empty()) std::memcpy(base + at, v.data(), bvbytes(v));
-    };
-    put(o.qlen, h.qlen);
-    put(o.tlen, h.tlen);
-    put(o.band, h.band);
-    put(o.order, h.order);
-    put(o.ptr_off, h.ptr_off);
-    put(o.bnd_off, h.bnd_off);
-    put(o.slot_off, h.slot_off);
-}
-
-void band_bind(ta_banded_plan* pl, uint8_t* d, const BandOffs& o) {
-    auto u32 = [&](uint64_t at) { return reinterpret_cast<uint32_t*>(d + at); };
-    auto u64 = [&](uint64_t at) { return reinterpret_cast<uint64_t*>(d + at); };
-    pl->d_qlen = u32(o.qlen);
-    pl->d_tlen = u32(o.tlen);
-    pl->d_band = u32(o.band);
-    pl->d_order = u32(o.order);
-    pl->d_ptr_off = u64(o.ptr_off);
-    pl->d_bnd_off = u64(o.bnd_off);
-    pl->d_slot_off = u64(o.slot_off);
-    pl->d_goal_i = u32(o.goal_i);
-    pl->d_goal_j = u32(o.goal_j);
-}
-
-// the range rule of include/team_align_c.h: every |value| < 2^26
-bool band_in_range(uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, int match, int mismatch, int gap) {
-    uint64_t maxn = 0, maxm = 0;
-    for (uint32_t p = 0; p < n_pairs; ++p) {
-        maxn = std::max<uint64_t>(maxn, qlen[p]);
-        maxm = std::max<uint64_t>(maxm, tlen[p]);
-    }
-    const long long pm = std::max({std::llabs(match), std::llabs(mismatch), std::llabs(gap)});
-    return (long long)(maxn + maxm + 2) * pm < (1ll << 26);
-}
-
 int band_check_args(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
                     const uint32_t* band, int type, int match, int mismatch, int gap) {
     if (!ctx) return TA_ERR_ARG;
     if (n_pairs && (!qlen || !tlen || !band)) return fail(ctx, TA_ERR_ARG, "null argument");
-    if (type != TA_GLOBAL && type != TA_LOCAL && type != TA_SEMI_GLOBAL)
-        return fail(ctx, TA_ERR_BAD_TYPE, ta_status_string(TA_ERR_BAD_TYPE));
-    if (!band_in_range(n_pairs, qlen, tlen, match, mismatch, gap))
+    if (!ta_host::valid_type(type)) return fail(ctx, TA_ERR_BAD_TYPE, ta_status_string(TA_ERR_BAD_TYPE));
+    if (!ta_host::in_range(n_pairs, qlen, tlen, std::max({std::llabs(match), std::llabs(mismatch), std::llabs(gap)})))
         return fail(ctx, TA_ERR_RANGE, ta_status_string(TA_ERR_RANGE));
     return TA_OK;
 }
 
-int band_check_io(ta_banded_plan* pl, const ta_device_io* io) {
-    if (!pl || !io) return TA_ERR_ARG;
-    if (pl->h.n_pairs && (!io->query_off || !io->target_off || !io->score || !io->target_begin))
-        return fail(pl->ctx, TA_ERR_ARG, "null device pointer");
-    if (pl->h.want_cigar && pl->h.n_pairs && (!io->cigar_slots || !io->cigar_start || !io->cigar_len))
-        return fail(pl->ctx, TA_ERR_ARG, "null cigar device pointer");
-    return TA_OK;
-}
+}  // namespace
 
-int band_exec_chunk(ta_banded_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace) {
+int ta_banded_plan::exec_chunk(ta_banded_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace) {
     ta_context* ctx = pl->ctx;
     const ta::BandPlan& h = pl->h;
     if (int r = ta_host::grow(ctx, ctx->ws_ptrs, h.ws_ptr_dwords * 4)) return r;
@@ -715,43 +575,9 @@ int band_exec_chunk(ta_banded_plan* pl, const ta_device_io* io, hipStream_t s, u
     return TA_OK;
 }
 
-int band_exec(ta_banded_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t chunk, bool fill, bool trace) {
-    ta_context* ctx = pl->ctx;
-    TA_HIP(ctx, hipSetDevice(ctx->device));
-    if (int r = ta_host::stream_enter(ctx, s)) return r;
-    const uint32_t c0 = chunk == UINT32_MAX ? 0 : chunk;
-    const uint32_t c1 = chunk == UINT32_MAX ? (uint32_t)pl->h.chunks.size() : chunk + 1;
-    for (uint32_t c = c0; c < c1; ++c)
-        if (int r = band_exec_chunk(pl, io, s, c, fill, trace)) return r;
-    return ta_host::stream_leave(ctx, s);
-}
-
-struct BandHostPlan final : ta_host::HostPlan {
-    ta_banded_plan* pl;
-    BandOffs o{};
-    explicit BandHostPlan(ta_banded_plan* p) : pl(p) {}
-    void layout(ta::BlockLayout& L) override { o = band_layout(pl->h, L); }
-    void pack(uint8_t* base) override { band_pack(pl->h, o, base); }
-    void layout_device_only(ta::BlockLayout& L) override { band_layout_scratch(pl->h, L, o); }
-    void bind(uint8_t* dev) override { band_bind(pl, dev, o); }
-    int execute(const ta_device_io* io, hipStream_t s) override { return band_exec(pl, io, s, UINT32_MAX, true, true); }
-    uint64_t slots_bytes() const override { return pl->h.slots_bytes; }
-    uint64_t err_offset() const override { return UINT64_MAX; }  // (no polls: one wave sweeps a pair's passes)
-    const char* err_message(uint32_t) const override { return ""; }
-};
-
-}  // namespace
-
 extern "C" {
 
-void ta_banded_plan_destroy(ta_banded_plan* pl) {
-    if (!pl) return;
-    if (pl->own_block) {
-        (void)hipSetDevice(pl->ctx->device);
-        (void)hipFree(pl->own_block);
-    }
-    delete pl;
-}
+void ta_banded_plan_destroy(ta_banded_plan* pl) { ta_host::plan_destroy(pl); }
 
 int ta_banded_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
                           const uint32_t* band, int type, int match, int mismatch, int gap, int want_cigar,
@@ -765,21 +591,7 @@ int ta_banded_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qle
     pl->ctx = ctx;
     ta::build_band_plan(pl->h, n_pairs, qlen, tlen, band, type, match, mismatch, gap, want_cigar != 0,
                         budget ? budget : ta_host::default_budget(ctx));
-    ta::BlockLayout L;
-    BandOffs o = band_layout(pl->h, L);
-    const uint64_t upload = L.bytes;
-    band_layout_scratch(pl->h, L, o);
-    std::vector<uint8_t> host(upload);
-    band_pack(pl->h, o, host.data());
-    hipError_t e = hipMalloc(&pl->own_block, std::max<uint64_t>(L.bytes, 256));
-    if (e == hipSuccess && upload) e = hipMemcpy(pl->own_block, host.data(), upload, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        ta_banded_plan_destroy(pl);
-        return fail(ctx, TA_ERR_DEVICE, std::string("ta_banded_plan_create: ") + hipGetErrorString(e));
-    }
-    band_bind(pl, static_cast<uint8_t*>(pl->own_block), o);
-    *out = pl;
-    return TA_OK;
+    return ta_host::plan_create_block(pl, "ta_banded_plan_create: ", out);
 }
 
 uint64_t ta_banded_plan_cigar_slots_bytes(const ta_banded_plan* pl) { return pl ? pl->h.slots_bytes : 0; }
@@ -791,52 +603,20 @@ uint64_t ta_banded_plan_band_cells(const ta_banded_plan* pl) { return pl ? pl->h
 uint64_t ta_banded_plan_swept_cells(const ta_banded_plan* pl) { return pl ? pl->h.swept_cells : 0; }
 
 int ta_banded_plan_pair_chunks(const ta_banded_plan* pl, uint32_t* chunk_of_pair) {
-    if (!pl || !chunk_of_pair) return TA_ERR_ARG;
-    for (uint32_t c = 0; c < (uint32_t)pl->h.chunks.size(); ++c) {
-        const auto& ch = pl->h.chunks[c];
-        for (uint32_t k = ch.begin; k < ch.begin + ch.count; ++k) chunk_of_pair[pl->h.order[k]] = c;
-    }
-    return TA_OK;
+    return ta_host::plan_pair_chunks(pl, chunk_of_pair);
 }
-
-int ta_banded_plan_check(ta_banded_plan* pl) { return pl ? TA_OK : TA_ERR_ARG; }
-
+int ta_banded_plan_check(ta_banded_plan* pl) { return ta_host::plan_check(pl); }
 int ta_banded_plan_execute(ta_banded_plan* pl, const ta_device_io* io, void* stream) {
-    if (int r = band_check_io(pl, io)) return r;
-    std::lock_guard<std::mutex> lock(pl->ctx->mu);
-    return band_exec(pl, io, (hipStream_t)stream, UINT32_MAX, true, true);
+    return ta_host::plan_execute(pl, io, stream);
 }
-
 int ta_banded_plan_execute_fill(ta_banded_plan* pl, const ta_device_io* io, void* stream, uint32_t chunk) {
-    if (int r = band_check_io(pl, io)) return r;
-    if (chunk >= pl->h.chunks.size()) return pl->h.n_pairs ? TA_ERR_ARG : TA_OK;
-    std::lock_guard<std::mutex> lock(pl->ctx->mu);
-    return band_exec(pl, io, (hipStream_t)stream, chunk, true, false);
+    return ta_host::plan_execute_chunk(pl, io, stream, chunk, true);
 }
-
 int ta_banded_plan_execute_traceback(ta_banded_plan* pl, const ta_device_io* io, void* stream, uint32_t chunk) {
-    if (int r = band_check_io(pl, io)) return r;
-    if (chunk >= pl->h.chunks.size()) return pl->h.n_pairs ? TA_ERR_ARG : TA_OK;
-    std::lock_guard<std::mutex> lock(pl->ctx->mu);
-    return band_exec(pl, io, (hipStream_t)stream, chunk, false, true);
+    return ta_host::plan_execute_chunk(pl, io, stream, chunk, false);
 }
-
 int ta_banded_plan_annotate(ta_banded_plan* pl, const ta_device_io* io, const ta_annotate_io* out, void* stream) {
-    if (!pl || !io || !out) return TA_ERR_ARG;
-    ta_context* ctx = pl->ctx;
-    if (!pl->h.want_cigar) return fail(ctx, TA_ERR_ARG, "annotate: the plan has no CIGARs");
-    if (out->eqx_slots && (!out->eqx_start || !out->eqx_len))
-        return fail(ctx, TA_ERR_ARG, "annotate: eqx_slots without eqx_start / eqx_len");
-    if (int r = band_check_io(pl, io)) return r;
-    if (!pl->h.n_pairs) return TA_OK;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    TA_HIP(ctx, hipSetDevice(ctx->device));
-    ta::AnnotateArgs a{pl->h.n_pairs, pl->h.type, pl->d_qlen, pl->d_tlen, pl->d_goal_i, pl->d_goal_j, pl->d_slot_off,
-                       reinterpret_cast<const uint8_t*>(io->query_bytes), io->query_off,
-                       reinterpret_cast<const uint8_t*>(io->target_bytes), io->target_off, io->cigar_slots,
-                       io->cigar_start, io->cigar_len, out->info, out->eqx_slots, out->eqx_start, out->eqx_len};
-    TA_HIP(ctx, ta::launch_annotate(a, (hipStream_t)stream));
-    return TA_OK;
+    return ta_host::plan_annotate(pl, io, out, stream);
 }
 
 int ta_align_batch_banded(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
@@ -860,8 +640,7 @@ int ta_align_batch_banded(ta_context* ctx, uint32_t n_pairs, const char* qb, con
     // everything in one chunk while the codes take at most 1 GiB (no device query per call)
     const uint64_t budget = need <= (1ull << 30) ? std::max<uint64_t>(need, 1) : ta_host::default_budget(ctx);
     ta::build_band_plan(pl.h, n_pairs, qlen, tlen, band, type, match, mismatch, gap, want_cigar != 0, budget);
-    BandHostPlan hp(&pl);
-    return ta_host::host_batch(ctx, hp, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
+    return ta_host::host_batch(ctx, pl, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
                                target_begin, arena, arena_bytes, cigar_off, cigar_len);
 }
 

@@ -1,6 +1,8 @@
 // bioinfo1_amd/csrc/ta_context.h -- the opaque ta_context of
 // include/team_align_c.h and the host helpers shared by the drivers of the
-// linear-gap plans (ta_api.hip) and the affine-gap extension (ta_affine.hip).
+// three plan families: linear gap (ta_api.hip), the affine-gap extension
+// (ta_affine.hip) and the banded extension (ta_banded.hip).  What those
+// drivers do alike with a plan is ta_plan_driver.h.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,0 +1,237 @@
+// bioinfo1_amd/csrc/ta_plan_block.h -- the device arrays of a plan, described
+// once per plan family (no HIP: builds with g++ for the CPU tests).
+//
+// A plan's per-pair arrays live in one device block (BlockLayout, 256-byte
+// aligned regions).  Each family has a struct of its device pointers and ONE
+// list of its arrays, block_arrays(h, d, v), which tells a visitor v, in block
+// order:
+//   v.vec(d.p, vector)   uploaded from a host vector of the plan (of p's element type)
+//   v.zeros(d.p, bytes)  uploaded as zeros (the error word, the ticket counters)
+//   v.device_only()      here ends what is uploaded
+//   v.scratch(d.p, n)    device-only scratch of n bytes
+// Layout, pack and bind below are three visitors of that list, so an array
+// added to it is sized, uploaded and bound at once.  The host-memory batch
+// driver (ta_host_batch.h) puts its own inputs between the uploaded and the
+// device-only part (`between` bytes).
+#pragma once
+
+#include <algorithm>
+#include <cstring>
+
+#include "ta_planner.h"
+
+namespace ta {
+
+// ---- linear gap (ta_api.hip)
+struct PlanArrays {
+    uint32_t *d_qlen = nullptr, *d_tlen = nullptr, *d_order = nullptr, *d_singles = nullptr, *d_duals = nullptr,
+             *d_flexes = nullptr;
+    uint64_t *d_ptr_off = nullptr, *d_bnd_off = nullptr, *d_slot_off = nullptr;
+    uint32_t *d_goal_i = nullptr, *d_goal_j = nullptr;
+    uint32_t* d_fb = nullptr;  // packed-fill hand-back: [n_dual_pairs] list, then one counter per chunk
+    uint32_t *d_flex_task_off = nullptr, *d_tickets = nullptr, *d_err = nullptr, *d_flex_tasks = nullptr;
+    void* d_pout = nullptr;   // PassOut[2] per flex task
+    void* d_dpout = nullptr;  // PassOut[2] per (pass, dual couple) of one multi-pass chunk
+    uint32_t* d_stask_off = nullptr;  // pipelined int32 fill: per single, its first task
+    uint64_t* d_stasks = nullptr;     // ... its tasks in ticket order
+    void* d_spout = nullptr;          // ... PassOut per task
+    uint8_t* d_pflag = nullptr;       // blk plans: per pair, handed back by the dual fill (band walk skips it)
+};
+
+// PassOut[2] (24 bytes each) per (pass, couple) of the largest multi-pass dual chunk
+inline uint64_t dual_pout_bytes(const Plan& h) {
+    uint64_t n = 0;
+    for (const auto& ch : h.chunks)
+        if (ch.dpasses > 1) n = std::max<uint64_t>(n, 2ull * ch.dcount * ch.dpasses);
+    return n * 24ull;
+}
+
+template <class V>
+void block_arrays(const Plan& h, PlanArrays& d, V& v) {
+    v.vec(d.d_qlen, h.qlen);
+    v.vec(d.d_tlen, h.tlen);
+    v.vec(d.d_order, h.order);
+    v.vec(d.d_singles, h.singles);
+    v.vec(d.d_duals, h.duals);
+    v.vec(d.d_flexes, h.flexes);
+    v.vec(d.d_flex_task_off, h.flex_task_off);
+    v.vec(d.d_flex_tasks, h.flex_tasks);
+    v.vec(d.d_stask_off, h.single_task_off);
+    v.vec(d.d_stasks, h.single_tasks);
+    v.vec(d.d_ptr_off, h.ptr_off);
+    v.vec(d.d_bnd_off, h.bnd_off);
+    v.vec(d.d_slot_off, h.slot_off);
+    v.zeros(d.d_err, 4);
+    v.zeros(d.d_tickets, 12ull * h.chunks.size());  // per chunk: flex, then dual, then pipelined int32
+    v.device_only();
+    v.scratch(d.d_goal_i, 4ull * h.n_pairs);
+    v.scratch(d.d_goal_j, 4ull * h.n_pairs);
+    v.scratch(d.d_fb, 4ull * (h.n_dual_pairs + h.chunks.size()));
+    v.scratch(d.d_pout, h.flexes.empty() ? 0 : h.flex_task_off.back() * 48ull + 16);
+    v.scratch(d.d_dpout, dual_pout_bytes(h));
+    v.scratch(d.d_spout, h.single_tasks.size() * 24ull);
+    v.scratch(d.d_pflag, h.blk ? h.n_pairs : 0);
+}
+
+// ---- affine gap (ta_affine.hip)
+struct AffineArrays {
+    uint32_t *d_qlen = nullptr, *d_tlen = nullptr, *d_order = nullptr, *d_goal_i = nullptr, *d_goal_j = nullptr;
+    uint32_t *d_singles = nullptr, *d_duals = nullptr;
+    uint32_t* d_fb = nullptr;  // hand-back list [2 * couples], then one counter per chunk
+    uint64_t *d_ptr_off = nullptr, *d_bnd_off = nullptr, *d_slot_off = nullptr;
+    uint32_t *d_err = nullptr, *d_tickets = nullptr;  // packed fill: poll error word, one ticket counter per chunk
+    void* d_pout = nullptr;                           // PassOut[2] per (pass, couple) of one chunk
+    uint32_t* d_stask_off = nullptr;  // pipelined int32 fill: per single, its first task
+    uint64_t* d_stasks = nullptr;     // ... its tasks in ticket order
+    void* d_spout = nullptr;          // ... PassOut per task
+};
+
+// PassOut[2] per (pass, couple) of the largest chunk (24-byte PassOut)
+inline uint64_t aff_pout_bytes(const AffinePlan& h) {
+    uint64_t n = 0;
+    for (const auto& ch : h.chunks) n = std::max<uint64_t>(n, 2ull * ch.dcount * ch.dpasses);
+    return n * 24ull;
+}
+
+template <class V>
+void block_arrays(const AffinePlan& h, AffineArrays& d, V& v) {
+    v.vec(d.d_qlen, h.qlen);
+    v.vec(d.d_tlen, h.tlen);
+    v.vec(d.d_order, h.order);
+    v.vec(d.d_singles, h.singles);
+    v.vec(d.d_duals, h.duals);
+    v.vec(d.d_stask_off, h.single_task_off);
+    v.vec(d.d_stasks, h.single_tasks);
+    v.vec(d.d_ptr_off, h.ptr_off);
+    v.vec(d.d_bnd_off, h.bnd_off);
+    v.vec(d.d_slot_off, h.slot_off);
+    v.zeros(d.d_err, 4);
+    v.zeros(d.d_tickets, 8ull * h.chunks.size());  // per chunk: packed, then pipelined int32
+    v.device_only();
+    v.scratch(d.d_goal_i, 4ull * h.n_pairs);
+    v.scratch(d.d_goal_j, 4ull * h.n_pairs);
+    v.scratch(d.d_fb, 4ull * (h.duals.size() + h.chunks.size()));
+    v.scratch(d.d_pout, aff_pout_bytes(h));
+    v.scratch(d.d_spout, h.single_tasks.size() * 24ull);
+}
+
+// ---- banded (ta_banded.hip)
+struct BandArrays {
+    uint32_t *d_qlen = nullptr, *d_tlen = nullptr, *d_band = nullptr, *d_order = nullptr;
+    uint32_t *d_goal_i = nullptr, *d_goal_j = nullptr;
+    uint64_t *d_ptr_off = nullptr, *d_bnd_off = nullptr, *d_slot_off = nullptr;
+};
+
+template <class V>
+void block_arrays(const BandPlan& h, BandArrays& d, V& v) {
+    v.vec(d.d_qlen, h.qlen);
+    v.vec(d.d_tlen, h.tlen);
+    v.vec(d.d_band, h.band);
+    v.vec(d.d_order, h.order);
+    v.vec(d.d_ptr_off, h.ptr_off);
+    v.vec(d.d_bnd_off, h.bnd_off);
+    v.vec(d.d_slot_off, h.slot_off);
+    v.device_only();
+    v.scratch(d.d_goal_i, 4ull * h.n_pairs);
+    v.scratch(d.d_goal_j, 4ull * h.n_pairs);
+}
+
+// ---- the three visitors
+template <class T>
+uint64_t vbytes(const std::vector<T>& v) {
+    return v.size() * sizeof(T);
+}
+
+// Where the parts of a block lie: [0, upload) is copied from the host,
+// [scratch, bytes) is device-only; scratch - upload = the caller's `between`.
+struct BlockSpan {
+    uint64_t upload = 0, scratch = 0, bytes = 0;
+};
+
+struct LayoutVisitor {
+    uint64_t between;
+    BlockLayout L;
+    BlockSpan span;
+    template <class T>
+    void vec(T*&, const std::vector<T>& v) {
+        L.add(vbytes(v));
+    }
+    template <class P>
+    void zeros(P*&, uint64_t n) {
+        L.add(n);
+    }
+    void device_only() {
+        span.upload = L.bytes;
+        span.scratch = L.bytes += between;
+    }
+    template <class P>
+    void scratch(P*&, uint64_t n) {
+        L.add(n);
+    }
+};
+
+// `between`: bytes the caller keeps between the two parts (a BlockLayout total, so a multiple of 256).
+template <class H, class D>
+BlockSpan layout_block(const H& h, D& d, uint64_t between = 0) {
+    LayoutVisitor v{between, {}, {}};
+    block_arrays(h, d, v);
+    v.span.bytes = v.L.bytes;
+    return v.span;
+}
+
+struct PackVisitor {
+    uint8_t* base;
+    BlockLayout L;
+    template <class T>
+    void vec(T*&, const std::vector<T>& v) {
+        const uint64_t at = L.add(vbytes(v));
+        if (!v.empty()) std::memcpy(base + at, v.data(), vbytes(v));
+    }
+    template <class P>
+    void zeros(P*&, uint64_t n) {
+        const uint64_t at = L.add(n);
+        if (n) std::memset(base + at, 0, n);
+    }
+    void device_only() {}
+    template <class P>
+    void scratch(P*&, uint64_t) {}
+};
+
+// Writes the uploaded part (BlockSpan::upload bytes) at base.
+template <class H, class D>
+void pack_block(const H& h, D& d, uint8_t* base) {
+    PackVisitor v{base, {}};
+    block_arrays(h, d, v);
+}
+
+struct BindVisitor {
+    uint8_t* base;
+    uint64_t scratch_at;
+    BlockLayout L;
+    template <class P>
+    void at(P*& p, uint64_t n) {
+        p = reinterpret_cast<P*>(base + L.add(n));
+    }
+    template <class T>
+    void vec(T*& p, const std::vector<T>& v) {
+        at(p, vbytes(v));
+    }
+    template <class P>
+    void zeros(P*& p, uint64_t n) {
+        at(p, n);
+    }
+    void device_only() { L.bytes = scratch_at; }
+    template <class P>
+    void scratch(P*& p, uint64_t n) {
+        at(p, n);
+    }
+};
+
+// Points d's members into the block at base (device-only part from span.scratch).
+template <class H, class D>
+void bind_block(const H& h, D& d, uint8_t* base, const BlockSpan& span) {
+    BindVisitor v{base, span.scratch, {}};
+    block_arrays(h, d, v);
+}
+
+}  // namespace ta

@@ -614,6 +614,55 @@ void build_affine_plan(AffinePlan& pl, uint32_t n_pairs, const uint32_t* qlen, c
     }
 }
 
+void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
+                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget) {
+    pl = BandPlan{};
+    pl.n_pairs = n_pairs;
+    pl.type = type;
+    pl.match = match;
+    pl.mismatch = mismatch;
+    pl.gap = gap;
+    pl.want_cigar = want_cigar;
+    pl.qlen.assign(qlen, qlen + n_pairs);
+    pl.tlen.assign(tlen, tlen + n_pairs);
+    pl.band.resize(n_pairs);
+    std::vector<uint64_t> swept(n_pairs);
+    pl.slot_off.resize(n_pairs);
+    for (uint32_t p = 0; p < n_pairs; ++p) {
+        pl.band[p] = band_clamp(qlen[p], tlen[p], band[p]);
+        swept[p] = band_swept_cells(qlen[p], tlen[p], pl.band[p]);
+        pl.swept_cells += swept[p];
+        pl.band_cells += band_cells(qlen[p], tlen[p], pl.band[p]);
+        pl.slot_off[p] = pl.slots_bytes;
+        pl.slots_bytes += cigar_slot_bytes(qlen[p], tlen[p]);
+    }
+    pl.order.resize(n_pairs);
+    std::iota(pl.order.begin(), pl.order.end(), 0u);
+    std::stable_sort(pl.order.begin(), pl.order.end(), [&](uint32_t x, uint32_t y) { return swept[x] > swept[y]; });
+    const uint64_t budget_dw = std::max<uint64_t>(budget / 4, 1);
+    pl.ptr_off.assign(n_pairs, 0);
+    pl.bnd_off.assign(n_pairs, 0);
+    BandPlan::Chunk c{0, 0, 0, 0};
+    for (uint32_t k = 0; k < n_pairs; ++k) {
+        const uint32_t p = pl.order[k];
+        const uint64_t codes = want_cigar ? band_ptr_dwords(qlen[p], tlen[p], pl.band[p]) : 0;
+        if (c.count && c.ptr_dwords + codes > budget_dw) {
+            pl.chunks.push_back(c);
+            c = {k, 0, 0, 0};
+        }
+        pl.ptr_off[p] = c.ptr_dwords;
+        pl.bnd_off[p] = c.bnd_words;
+        c.ptr_dwords += codes;
+        c.bnd_words += bnd_words(qlen[p], tlen[p]);
+        ++c.count;
+    }
+    if (c.count) pl.chunks.push_back(c);
+    for (const auto& ch : pl.chunks) {
+        pl.ws_ptr_dwords = std::max(pl.ws_ptr_dwords, ch.ptr_dwords);
+        pl.ws_bnd_words = std::max(pl.ws_bnd_words, ch.bnd_words);
+    }
+}
+
 uint64_t host_batch_code_bytes(uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, uint64_t bytes_per_entry) {
     uint64_t need = 0;
     for (uint32_t p = 0; p < n_pairs; ++p) need += ptr_dwords_blk(qlen[p], tlen[p]) * bytes_per_entry;

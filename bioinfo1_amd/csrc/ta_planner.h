@@ -1,9 +1,11 @@
 // bioinfo1_amd/csrc/ta_planner.h -- host planning of a batch (no HIP):
 // which kernel each pair runs in, the visit order, the chunks the 2-bit
 // traceback-code workspace is cut into, and every per-pair offset the kernels
-// read.  The device side (ta_api.hip / ta_affine.hip) uploads the arrays
-// packed into one block and launches per chunk.  Pure C++ so that it builds
-// with g++ for the CPU tests and the ASan/UBSan/TSan runs (tests/test_host_sanitizers.py).
+// read, for the three plan families: linear gap, affine gap and banded.  The
+// device side (ta_api.hip / ta_affine.hip / ta_banded.hip, through
+// ta_plan_driver.h) uploads the arrays packed into one block (ta_plan_block.h)
+// and launches per chunk.  Pure C++ so that it builds with g++ for the CPU
+// tests and the ASan/UBSan/TSan runs (tests/test_host_sanitizers.py).
 #pragma once
 
 #include <stdint.h>
@@ -130,6 +132,28 @@ struct AffinePlan {
 void build_affine_plan(AffinePlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, int type,
                        int match, int mismatch, int gap_open, int gap_extend, bool want_cigar, uint64_t budget,
                        uint32_t flags, uint32_t wave_quantum = 0);
+
+// Banded plan (the banded extension of include/team_align_c.h): pairs by
+// descending swept cells (the long ones start first), chunks closed when the
+// next pair's codes would pass the budget.
+struct BandPlan {
+    uint32_t n_pairs = 0;
+    int type = 0, match = 0, mismatch = 0, gap = 0;
+    bool want_cigar = false;
+    std::vector<uint32_t> qlen, tlen, band, order;
+    std::vector<uint64_t> ptr_off, bnd_off, slot_off;
+    struct Chunk {
+        uint32_t begin, count;
+        uint64_t ptr_dwords, bnd_words;
+    };
+    std::vector<Chunk> chunks;
+    uint64_t slots_bytes = 0, ws_ptr_dwords = 0, ws_bnd_words = 0;
+    uint64_t band_cells = 0, swept_cells = 0;
+};
+
+// budget = bytes of 2-bit codes per chunk (> 0); band[p] is clamped to its pair (ta_layout.h band_clamp).
+void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
+                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget);
 
 // One contiguous block holding several arrays, each at a 256-byte aligned
 // offset: the plan's per-pair arrays go to the device in one copy.

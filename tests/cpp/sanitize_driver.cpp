@@ -8,6 +8,9 @@
 //   planner SEED N T the host planner (bioinfo1_amd/csrc/ta_planner.cpp) on N
 //                    random batches from T threads at once: every pair planned
 //                    exactly once, chunk / workspace / task invariants
+//                    (linear, affine and, at four band widths, banded plans)
+//   blocks SEED N    the plans' device blocks (ta_plan_block.h) on N such
+//                    batches: layout, pack and bind against host buffers
 //   fastx PATH Q     the FASTA/FASTQ reader (tm_fastx.cpp): record count + checksum
 #include <algorithm>
 #include <cstdint>
@@ -21,6 +24,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../bioinfo1_amd/csrc/ta_plan_block.h"
 #include "../../bioinfo1_amd/csrc/ta_planner.h"
 #include "../../bioinfo1_amd/csrc/tm_fastx.h"
 
@@ -245,36 +249,188 @@ void check_affine(const ta::AffinePlan& pl) {
     }
 }
 
+void check_band(const ta::BandPlan& pl, uint32_t width) {
+    const uint32_t P = pl.n_pairs;
+    std::vector<int> seen(P, 0);
+    for (uint32_t x : pl.order) {
+        CHECK(x < P);
+        if (x < P) ++seen[x];
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+        CHECK(seen[p] == 1);
+        CHECK(pl.band[p] == ta::band_clamp(pl.qlen[p], pl.tlen[p], width) && pl.band[p] <= width);
+    }
+    uint64_t count = 0;
+    for (const auto& c : pl.chunks) {  // chunks tile the order
+        CHECK(c.begin == count && c.count > 0);
+        count += c.count;
+        CHECK(c.ptr_dwords <= pl.ws_ptr_dwords);
+        CHECK(c.bnd_words <= pl.ws_bnd_words);
+        for (uint32_t k = c.begin; k < c.begin + c.count && k < P; ++k) {
+            const uint32_t x = pl.order[k];
+            const uint64_t need = pl.want_cigar ? ta::band_ptr_dwords(pl.qlen[x], pl.tlen[x], pl.band[x]) : 0;
+            CHECK(pl.ptr_off[x] + need <= c.ptr_dwords);
+            CHECK(pl.bnd_off[x] + ta::bnd_words(pl.qlen[x], pl.tlen[x]) <= c.bnd_words);
+        }
+    }
+    CHECK(count == P);
+    uint64_t so = 0;
+    for (uint32_t p = 0; p < P; ++p) {
+        CHECK(pl.slot_off[p] == so);
+        so += ta::cigar_slot_bytes(pl.qlen[p], pl.tlen[p]);
+    }
+    CHECK(so == pl.slots_bytes);
+}
+
+constexpr uint32_t kBandWidths[] = {0, 1, 37, 5000};  // (5000 clamps on most shapes below)
+
+// One random batch and plan settings (the shapes of the planner and blocks modes).
+struct Batch {
+    std::vector<uint32_t> q, t;
+    int type, ma, mi, g;
+    uint64_t budget;
+    uint32_t flags, quantum;
+    bool cig;
+};
+
+Batch random_batch(uint64_t& s) {
+    Batch b;
+    std::vector<uint32_t>&q = b.q, &t = b.t;
+    const int kind = (int)(splitmix(s) % 5);
+    const uint32_t P = kind == 4 ? 2 + (uint32_t)(splitmix(s) % 3) : (uint32_t)(splitmix(s) % 300);
+    q.resize(P);
+    t.resize(P);
+    for (uint32_t p = 0; p < P; ++p) {
+        switch (kind) {
+            case 0: q[p] = t[p] = 1000; break;                                                 // config 2
+            case 1: q[p] = (uint32_t)(splitmix(s) % 3000); t[p] = (uint32_t)(splitmix(s) % 3000); break;  // ragged
+            case 2: q[p] = 1 + (uint32_t)(splitmix(s) % 20000); t[p] = q[p] + (uint32_t)(splitmix(s) % 500); break;
+            case 3: q[p] = (uint32_t)(splitmix(s) % 4) * 1024 + 7; t[p] = 300 + (uint32_t)(splitmix(s) % 3); break;
+            default: q[p] = 63 * 1024 + 1 + (uint32_t)(splitmix(s) % 3) * 1024; t[p] = 40; break;  // 63..65 passes
+        }
+    }
+    b.type = (int)(splitmix(s) % 3);
+    // (kind 4: all-zero scoring, whose values fit int16 at any length: only the pass bound stops couples)
+    b.ma = kind == 4 ? 0 : 1 + (int)(splitmix(s) % 3);
+    b.mi = kind == 4 ? 0 : -(int)(splitmix(s) % 3);
+    b.g = kind == 4 ? 0 : -(int)(splitmix(s) % 3);
+    b.budget = (splitmix(s) & 1) ? (1ull << 40) : 4096ull + splitmix(s) % (64ull << 20);
+    b.flags = (uint32_t)(splitmix(s) % 8) | ((splitmix(s) & 1) ? 32u : 0u) | ((splitmix(s) & 1) ? 64u : 0u);
+    b.cig = splitmix(s) % 4 != 0;
+    b.quantum = (splitmix(s) & 1) ? 1024u : (uint32_t)(splitmix(s) % 9);
+    return b;
+}
+
+// The three families' plans of one batch, each handed to `check(plan, ...)`-style callbacks.
+template <class Linear, class Affine, class Banded>
+void plan_batch(const Batch& b, Linear on_linear, Affine on_affine, Banded on_banded) {
+    const uint32_t P = (uint32_t)b.q.size();
+    ta::Plan pl;
+    ta::build_plan(pl, P, b.q.data(), b.t.data(), b.type, b.ma, b.mi, b.g, b.cig, b.budget, b.flags, b.quantum);
+    on_linear(pl);
+    ta::AffinePlan ap;
+    ta::build_affine_plan(ap, P, b.q.data(), b.t.data(), b.type, b.ma, b.mi, -2, b.g, b.cig, b.budget, b.flags & 97u,
+                          b.quantum);
+    on_affine(ap);
+    for (uint32_t w : kBandWidths) {
+        const std::vector<uint32_t> band(P, w);
+        ta::BandPlan bp;
+        ta::build_band_plan(bp, P, b.q.data(), b.t.data(), band.data(), b.type, b.ma, b.mi, b.g, b.cig, b.budget);
+        on_banded(bp, w);
+    }
+}
+
 void plan_worker(uint64_t seed, int iters) {
     uint64_t s = seed;
     for (int it = 0; it < iters; ++it) {
-        const int kind = (int)(splitmix(s) % 5);
-        const uint32_t P = kind == 4 ? 2 + (uint32_t)(splitmix(s) % 3) : (uint32_t)(splitmix(s) % 300);
-        std::vector<uint32_t> q(P), t(P);
-        for (uint32_t p = 0; p < P; ++p) {
-            switch (kind) {
-                case 0: q[p] = t[p] = 1000; break;                                                 // config 2
-                case 1: q[p] = (uint32_t)(splitmix(s) % 3000); t[p] = (uint32_t)(splitmix(s) % 3000); break;  // ragged
-                case 2: q[p] = 1 + (uint32_t)(splitmix(s) % 20000); t[p] = q[p] + (uint32_t)(splitmix(s) % 500); break;
-                case 3: q[p] = (uint32_t)(splitmix(s) % 4) * 1024 + 7; t[p] = 300 + (uint32_t)(splitmix(s) % 3); break;
-                default: q[p] = 63 * 1024 + 1 + (uint32_t)(splitmix(s) % 3) * 1024; t[p] = 40; break;  // 63..65 passes
-            }
-        }
-        const int type = (int)(splitmix(s) % 3);
-        // (kind 4: all-zero scoring, whose values fit int16 at any length: only the pass bound stops couples)
-        const int ma = kind == 4 ? 0 : 1 + (int)(splitmix(s) % 3), mi = kind == 4 ? 0 : -(int)(splitmix(s) % 3),
-                  g = kind == 4 ? 0 : -(int)(splitmix(s) % 3);
-        const uint64_t budget = (splitmix(s) & 1) ? (1ull << 40) : 4096ull + splitmix(s) % (64ull << 20);
-        const uint32_t flags = (uint32_t)(splitmix(s) % 8) | ((splitmix(s) & 1) ? 32u : 0u) | ((splitmix(s) & 1) ? 64u : 0u);
-        const bool cig = splitmix(s) % 4 != 0;
-        ta::Plan pl;
-        const uint32_t quantum = (splitmix(s) & 1) ? 1024u : (uint32_t)(splitmix(s) % 9);
-        ta::build_plan(pl, P, q.data(), t.data(), type, ma, mi, g, cig, budget, flags, quantum);
-        check_linear(pl, budget);
-        ta::AffinePlan ap;
-        ta::build_affine_plan(ap, P, q.data(), t.data(), type, ma, mi, -2, g, cig, budget, flags & 97u, quantum);
-        check_affine(ap);
+        const Batch b = random_batch(s);
+        plan_batch(
+            b, [&](const ta::Plan& pl) { check_linear(pl, b.budget); }, [](const ta::AffinePlan& ap) { check_affine(ap); },
+            [](const ta::BandPlan& bp, uint32_t w) { check_band(bp, w); });
     }
+}
+
+// ---- blocks mode: a plan's device block (ta_plan_block.h) against host buffers.
+// Walks the bound block in list order, as the fourth visitor of the list: it
+// checks what layout, pack and bind made of the list, not the list itself.
+// That the list holds every member of the family's pointer struct, once each,
+// rests on check_block's count of the listed entries against the struct's
+// pointers and on its sweep for a pointer left unbound.
+struct BlockChecker {
+    const uint8_t* base;
+    ta::BlockSpan span;
+    const uint8_t* end;  // end of the previous region
+    bool device_part = false;
+    size_t entries = 0;
+    void region(const void* ptr, uint64_t n) {
+        const uint8_t* p = static_cast<const uint8_t*>(ptr);
+        CHECK(reinterpret_cast<uintptr_t>(p) % 256 == 0);
+        CHECK(p >= end);  // disjoint, in list order
+        if (device_part) CHECK(p >= base + span.scratch);
+        else CHECK(p + n <= base + span.upload);
+        CHECK(p + n <= base + span.bytes);
+        end = p + n;
+        ++entries;
+    }
+    template <class T>
+    void vec(T*& p, const std::vector<T>& v) {
+        region(p, ta::vbytes(v));
+        if (!v.empty()) CHECK(std::memcmp(p, v.data(), ta::vbytes(v)) == 0);
+    }
+    template <class P>
+    void zeros(P*& p, uint64_t n) {
+        region(p, n);
+        const uint8_t* z = reinterpret_cast<const uint8_t*>(p);
+        for (uint64_t k = 0; k < n; ++k) CHECK(z[k] == 0);
+    }
+    void device_only() {
+        CHECK(uint64_t(end - base) <= span.upload && span.upload - uint64_t(end - base) < 256);
+        device_part = true;
+    }
+    template <class P>
+    void scratch(P*& p, uint64_t n) {
+        region(p, n);
+    }
+};
+
+// D: the family's device-array struct (pointers only).
+template <class D, class H>
+void check_block(const H& h, uint64_t between) {
+    D d;
+    const ta::BlockSpan span = ta::layout_block(h, d, between);
+    CHECK(span.upload % 256 == 0 && span.scratch == span.upload + between && span.bytes >= span.scratch);
+    // pack into a buffer of the uploaded part, "upload" it into the whole block, bind there
+    std::vector<uint8_t> up(span.upload, 0xA5);
+    ta::pack_block(h, d, up.data());
+    uint8_t* blk = static_cast<uint8_t*>(std::aligned_alloc(256, std::max<uint64_t>(span.bytes, 256)));
+    std::memset(blk, 0x5A, std::max<uint64_t>(span.bytes, 256));
+    if (span.upload) std::memcpy(blk, up.data(), span.upload);
+    ta::bind_block(h, d, blk, span);
+    void* ptrs[sizeof(D) / sizeof(void*)];  // no member left unbound
+    static_assert(sizeof(D) % sizeof(void*) == 0, "device arrays: pointers only");
+    std::memcpy(ptrs, &d, sizeof(D));
+    for (void* p : ptrs) CHECK(p >= (void*)blk && p <= (void*)(blk + span.bytes));
+    BlockChecker v{blk, span, blk};
+    ta::block_arrays(h, d, v);
+    CHECK(v.device_part);
+    CHECK(v.entries == sizeof(D) / sizeof(void*));  // every member listed (one listed twice leaves another unbound, for the sweep above)
+    CHECK(((uint64_t(v.end - blk) + 255) & ~uint64_t(255)) == span.bytes);  // the total ends the last region
+    std::free(blk);
+}
+
+int run_blocks(uint64_t seed, int iters) {
+    uint64_t s = seed;
+    uint64_t blocks = 0;
+    for (int it = 0; it < iters; ++it) {
+        const Batch b = random_batch(s);
+        const uint64_t between = (it & 1) ? 0 : 256 * (1 + splitmix(s) % 5);  // (a host batch's own inputs)
+        plan_batch(
+            b, [&](const ta::Plan& pl) { check_block<ta::PlanArrays>(pl, between), ++blocks; },
+            [&](const ta::AffinePlan& ap) { check_block<ta::AffineArrays>(ap, between), ++blocks; },
+            [&](const ta::BandPlan& bp, uint32_t) { check_block<ta::BandArrays>(bp, between), ++blocks; });
+    }
+    std::printf("blocks %llu fails %d\n", (unsigned long long)blocks, fails);
+    return fails ? 1 : 0;
 }
 
 // Small host batches (the drop-in call's combined batches, ta_align_batch)
@@ -352,7 +508,9 @@ int main(int argc, char** argv) {
     if (argc >= 3 && std::strcmp(argv[1], "oracle") == 0) return run_oracle(argv[2]);
     if (argc >= 5 && std::strcmp(argv[1], "planner") == 0)
         return run_planner(std::strtoull(argv[2], nullptr, 10), std::atoi(argv[3]), std::atoi(argv[4]));
+    if (argc >= 4 && std::strcmp(argv[1], "blocks") == 0)
+        return run_blocks(std::strtoull(argv[2], nullptr, 10), std::atoi(argv[3]));
     if (argc >= 4 && std::strcmp(argv[1], "fastx") == 0) return run_fastx(argv[2], std::atoi(argv[3]) != 0);
-    std::fprintf(stderr, "usage: %s oracle CASES | planner SEED N THREADS | fastx PATH FASTQ\n", argv[0]);
+    std::fprintf(stderr, "usage: %s oracle CASES | planner SEED N THREADS | blocks SEED N | fastx PATH FASTQ\n", argv[0]);
     return 2;
 }

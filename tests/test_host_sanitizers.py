@@ -2,7 +2,8 @@
 detection / sanitizers).  Built here with g++/gcc, no GPU:
 
 * ASan + UBSan: the oracle (align_oracle.c, affine_oracle.c) on every golden
-  case, the host planner (ta_planner.cpp) on random batches, the FASTA/FASTQ
+  case, the host planner (ta_planner.cpp) on random batches, the plans' device
+  blocks (ta_plan_block.h: layout, pack, bind) on such batches, the FASTA/FASTQ
   reader (tm_fastx.cpp) on the committed mapper inputs (plain and gzip);
 * TSan: the planner from 8 threads at once, and the drop-in team::Align shim
   (team_alignment_shim.cpp: per-thread contexts and buffers) called from 4
@@ -70,6 +71,11 @@ def test_oracle_asan_ubsan(asan_driver):
 
 def test_planner_asan_ubsan(asan_driver):
     assert "fails 0" in _run([asan_driver, "planner", "12345", "150", "1"])
+
+
+def test_blocks_asan_ubsan(asan_driver):
+    out = _run([asan_driver, "blocks", "4242", "60"])
+    assert "fails 0" in out and int(out.split("blocks ")[1].split()[0]) == 60 * 6  # linear, affine, 4 band widths
 
 
 def test_fastx_asan_ubsan(asan_driver):
