@@ -107,6 +107,10 @@ def lib() -> C.CDLL:
     L.ta_plan_execute_traceback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.ta_pipeline_create.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]
     L.ta_pipeline_create_affine.argtypes = L.ta_pipeline_create.argtypes
+    L.ta_pipeline_create_ex.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p)]
+    L.ta_pipeline_create_affine_ex.argtypes = L.ta_pipeline_create_ex.argtypes
+    L.ta_pipeline_walk_streams.argtypes = [C.c_void_p]
+    L.ta_pipeline_walk_streams.restype = C.c_uint32
     L.ta_pipeline_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u32p]
     L.ta_pipeline_destroy.argtypes = [C.c_void_p]
     L.ta_pipeline_destroy.restype = None
@@ -181,6 +185,7 @@ ABI_SYMBOLS = [
     "ta_plan_annotate", "ta_affine_plan_annotate",
     "ta_plan_context", "ta_affine_plan_context", "ta_context_device",
     "ta_pipeline_create", "ta_pipeline_create_affine", "ta_pipeline_step", "ta_pipeline_destroy",
+    "ta_pipeline_create_ex", "ta_pipeline_create_affine_ex", "ta_pipeline_walk_streams",
 ]
 # The banded extension's symbols (checked by tests/test_banded_ref.py).
 BANDED_ABI_SYMBOLS = [
@@ -757,7 +762,8 @@ class DevicePipeline:
     shared first batch).  Memory: ``depth`` workspaces (3 by default)."""
 
     def __init__(self, device: int, batch, type, match, mismatch, gap, want_cigar=True, depth: int = 3,
-                 workspace_budget: int = 0, gap_open=None, flags: int = 0, inputs=None, first=None):
+                 workspace_budget: int = 0, gap_open=None, flags: int = 0, inputs=None, first=None,
+                 walk_streams=None):
         """first: an existing DevicePlan (on its own Aligner) to use as slot 0;
         the other slots then start on its inputs.  depth: the slots (>= 2).
         At 2, fill k+2 waits for walk k, which ends only shortly before fill
@@ -765,7 +771,11 @@ class DevicePipeline:
         a fill is always queued behind the running one (DESIGN 3.12 has the
         measurements; 4 was slower).  A caller that rotates its batches to
         check the pipeline wants a count coprime with the depth, or every
-        slot realigns the batch it held last."""
+        slot realigns the batch it held last.  walk_streams: the walk streams
+        (1 .. depth; step k's traceback runs on stream k % walk_streams, so
+        consecutive walks may overlap); None: the library's default, which
+        depends on GPU_MAX_HW_QUEUES (ta_pipeline_create_ex in
+        team_align_c.h).  ``self.walk_streams`` is the count in use."""
         import torch
 
         self.torch = torch
@@ -785,8 +795,9 @@ class DevicePipeline:
         L = lib()
         handles = (C.c_void_p * len(self.plans))(*[p._h for p in self.plans])
         h = C.c_void_p()
-        create = L.ta_pipeline_create_affine if self.plans[0].affine else L.ta_pipeline_create
-        r = create(handles, len(self.plans), C.byref(h))
+        create = L.ta_pipeline_create_affine_ex if self.plans[0].affine else L.ta_pipeline_create_ex
+        opts = (C.c_uint32 * 2)(8, int(walk_streams or 0))  # ta_pipeline_options: size, walk_streams
+        r = create(handles, len(self.plans), opts, C.byref(h))
         if r != TA_OK:
             msg = L.ta_last_error(self.plans[0]._ctx).decode()
             for p in self.plans[1 if first is not None else 0:]:  # (a caller's ``first`` stays open)
@@ -797,6 +808,7 @@ class DevicePipeline:
                 raise ValueError(msg or "ta_pipeline_create: invalid argument")
             raise DeviceError(f"{L.ta_status_string(r).decode()}: {msg}")
         self._h = h
+        self.walk_streams = L.ta_pipeline_walk_streams(h)
 
     @property
     def chunks(self):

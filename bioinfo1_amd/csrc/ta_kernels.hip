@@ -966,6 +966,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(1, 1))) v
 
 // ... and their runs into CIGAR text, one wave per pair.
 __global__ __launch_bounds__(kBlock) void format_runs_kernel(TraceArgs a) {
+    // throughput work of 22 VGPRs that fits beside a SIMD's five fill waves (align.DevicePipeline):
+    // ahead of them at the issue arbiter it is done in its own issue time, not in a one-sixth share
+    __builtin_amdgcn_s_setprio(3);
     const uint32_t w = wave_id();
     if (w >= a.count) return;
     format_runs(a, a.order ? a.order[a.begin + w] : a.begin + w, threadIdx.x & 63);

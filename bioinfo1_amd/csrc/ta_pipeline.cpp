@@ -13,11 +13,21 @@
 // fill k+1, which runs on another slot's stream: when fill k+1's last blocks
 // run alone on a mostly idle chip (they could not become resident while walk
 // k held registers), fill k+2's blocks take the free CUs.
+//
+// WALK STREAMS: ta_pipeline_create keeps one, so walks and their formatters run
+// back to back.  With walk_streams = w (ta_pipeline_create_ex) step k's
+// traceback goes to walk stream k % w -- the step index, not the slot's, so
+// consecutive steps alternate whatever the depth -- and walk k+1 may start
+// beside walk k's tail and its formatter.  Nothing else changes: a walk still
+// follows its own fill through the slot's context, the caller's stream waits
+// for every step's walk in step order, and a fill for its slot's done event.
 #ifndef __HIP_PLATFORM_AMD__
 #define __HIP_PLATFORM_AMD__ 1
 #endif
 #include <hip/hip_runtime_api.h>
 
+#include <cstddef>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -77,7 +87,7 @@ struct ta_pipeline {
     std::vector<ta_context*> ctxs;
     // created at the first step (each stream takes one of the process's few hardware queues)
     std::vector<hipStream_t> fill;  // one per slot
-    hipStream_t walk = nullptr;     // high priority: a hardware queue of its own beside the fills'
+    std::vector<hipStream_t> walk;  // step k's traceback on walk[k % size]; high priority: hardware queues beside the fills'
     // done[s]: recorded on the caller's stream at the step after slot s's, so it covers
     // slot s's traceback and what the caller queued after it; walked[s]: slot s's traceback;
     // start: the caller's stream at the first step (a slot's first fill follows it)
@@ -90,7 +100,25 @@ struct ta_pipeline {
 
 namespace {
 
-int create(const Ops& ops, void* const* slots, uint32_t depth, ta_pipeline** out) {
+// GPU_MAX_HW_QUEUES as the HIP runtime reads it: unset (or not a number) is its default, 4.
+uint32_t hw_queues() {
+    const char* v = std::getenv("GPU_MAX_HW_QUEUES");
+    if (!v || !*v) return 4;
+    char* end = nullptr;
+    const long n = std::strtol(v, &end, 10);
+    return (*end || n <= 0) ? 4u : (uint32_t)n;
+}
+
+// walk_streams 0: the library's default where every stream of the pipeline and the caller's
+// get a hardware queue of their own (streams sharing a queue run one after the other, and a
+// walk behind a fill on its queue would be worse than the one walk stream); else one.
+uint32_t resolve_walk_streams(uint32_t asked, uint32_t depth) {
+    if (asked) return asked;
+    const uint32_t w = TA_PIPELINE_WALK_STREAMS_DEFAULT < depth ? TA_PIPELINE_WALK_STREAMS_DEFAULT : depth;
+    return hw_queues() >= depth + w + 1 ? w : 1;
+}
+
+int create(const Ops& ops, void* const* slots, uint32_t depth, const ta_pipeline_options* opt, ta_pipeline** out) {
     if (!out) return TA_ERR_ARG;
     *out = nullptr;
     if (!slots || !depth || !slots[0]) return TA_ERR_ARG;
@@ -106,12 +134,22 @@ int create(const Ops& ops, void* const* slots, uint32_t depth, ta_pipeline** out
             if (ops.context(slots[b]) == ca)
                 return fail(c0, TA_ERR_ARG, "ta_pipeline_create: two slots share a context (each needs its own workspace)");
     }
+    // (fields beyond the caller's `size` read as 0; no options: ta_pipeline_create's one walk stream)
+    uint32_t w = 1;
+    if (opt) {
+        const bool has = opt->size >= offsetof(ta_pipeline_options, walk_streams) + sizeof(opt->walk_streams);
+        w = resolve_walk_streams(has ? opt->walk_streams : 0, depth);
+    }
+    if (w > depth)
+        return fail(c0, TA_ERR_ARG, "ta_pipeline_create: walk_streams exceeds depth (" + std::to_string(w) + " > " +
+                                        std::to_string(depth) + ")");
     auto* p = new ta_pipeline();
     p->ops = &ops;
     p->device = ta_context_device(c0);
     p->slots.assign(slots, slots + depth);
     for (uint32_t a = 0; a < depth; ++a) p->ctxs.push_back(ops.context(slots[a]));
     p->fill.assign(depth, nullptr);
+    p->walk.assign(w, nullptr);
     p->done.assign(depth, nullptr);
     p->walked.assign(depth, nullptr);
     p->used.assign(depth, false);
@@ -142,12 +180,26 @@ int lazy_event(ta_context* ctx, hipEvent_t& e) {
 extern "C" {
 
 int ta_pipeline_create(ta_plan* const* slots, uint32_t depth, ta_pipeline** out) {
-    return create(kLinear, reinterpret_cast<void* const*>(slots), depth, out);
+    return create(kLinear, reinterpret_cast<void* const*>(slots), depth, nullptr, out);
+}
+
+int ta_pipeline_create_ex(ta_plan* const* slots, uint32_t depth, const ta_pipeline_options* options,
+                          ta_pipeline** out) {
+    const ta_pipeline_options defaults = {sizeof(ta_pipeline_options), 0};
+    return create(kLinear, reinterpret_cast<void* const*>(slots), depth, options ? options : &defaults, out);
 }
 
 int ta_pipeline_create_affine(ta_affine_plan* const* slots, uint32_t depth, ta_pipeline** out) {
-    return create(kAffine, reinterpret_cast<void* const*>(slots), depth, out);
+    return create(kAffine, reinterpret_cast<void* const*>(slots), depth, nullptr, out);
 }
+
+int ta_pipeline_create_affine_ex(ta_affine_plan* const* slots, uint32_t depth, const ta_pipeline_options* options,
+                                 ta_pipeline** out) {
+    const ta_pipeline_options defaults = {sizeof(ta_pipeline_options), 0};
+    return create(kAffine, reinterpret_cast<void* const*>(slots), depth, options ? options : &defaults, out);
+}
+
+uint32_t ta_pipeline_walk_streams(const ta_pipeline* p) { return p ? (uint32_t)p->walk.size() : 0; }
 
 int ta_pipeline_step(ta_pipeline* p, const ta_device_io* io, void* ready_event, void* caller_stream,
                      uint32_t* slot_out) {
@@ -158,11 +210,13 @@ int ta_pipeline_step(ta_pipeline* p, const ta_device_io* io, void* ready_event, 
     if (!io) return fail(ctx, TA_ERR_ARG, "ta_pipeline_step: null io");
     hipStream_t cur = static_cast<hipStream_t>(caller_stream);
     TP_HIP(ctx, hipSetDevice(p->device));
-    if (!p->walk) {
+    if (!p->walk.back()) {  // every walk stream at the first step
         int least = 0, greatest = 0;
         TP_HIP(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        if (int r = lazy_stream(ctx, p->walk, greatest)) return r;
+        for (hipStream_t& s : p->walk)
+            if (int r = lazy_stream(ctx, s, greatest)) return r;
     }
+    hipStream_t walk = p->walk[p->k % p->walk.size()];
     if (int r = lazy_stream(ctx, p->fill[i], 0)) return r;
     if (int r = lazy_event(ctx, p->done[i])) return r;
     if (int r = lazy_event(ctx, p->walked[i])) return r;
@@ -179,9 +233,9 @@ int ta_pipeline_step(ta_pipeline* p, const ta_device_io* io, void* ready_event, 
     const uint32_t chunks = p->ops->chunks(plan);
     for (uint32_t c = 0; c < chunks; ++c) {
         if (int r = p->ops->fill(plan, io, p->fill[i], c)) return r;
-        if (int r = p->ops->walk(plan, io, p->walk, c)) return r;  // (after the fill: the slot's context orders them)
+        if (int r = p->ops->walk(plan, io, walk, c)) return r;  // (after the fill: the slot's context orders them)
     }
-    TP_HIP(ctx, hipEventRecord(p->walked[i], p->walk));
+    TP_HIP(ctx, hipEventRecord(p->walked[i], walk));
     TP_HIP(ctx, hipStreamWaitEvent(cur, p->walked[i], 0));
     p->used[i] = true;
     p->last = (int)i;
@@ -195,7 +249,8 @@ void ta_pipeline_destroy(ta_pipeline* p) {
     // (destroying a stream or an event with work pending is deferred by the runtime until it is done)
     for (hipStream_t s : p->fill)
         if (s) (void)hipStreamDestroy(s);
-    if (p->walk) (void)hipStreamDestroy(p->walk);
+    for (hipStream_t s : p->walk)
+        if (s) (void)hipStreamDestroy(s);
     for (hipEvent_t e : p->done)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : p->walked)

@@ -275,6 +275,43 @@ int ta_pipeline_step(ta_pipeline* pipe, const ta_device_io* io, void* ready_even
                      uint32_t* slot_out);
 void ta_pipeline_destroy(ta_pipeline* pipe);
 
+/*
+ * ta_pipeline_create with options.  `size` is sizeof(ta_pipeline_options) as
+ * the caller was compiled (fields beyond it read as 0); a NULL `options` is
+ * every field 0.  A field of 0 means the library's default.
+ *
+ * walk_streams = w (1 <= w <= depth; larger: TA_ERR_ARG, the message names
+ * walk_streams): the pipeline owns w walk streams, all of high priority and
+ * created at the first step, and step k's traceback (every chunk) runs on walk
+ * stream k % w -- consecutive steps on different streams, so walk k+1 may
+ * start beside walk k's tail and its run formatter instead of behind them.
+ * Everything else is as above: a walk follows its own fill, the caller's
+ * stream waits for every step's traceback in step order, a fill for its
+ * slot's previous use only.  Results are the same bytes for every w.
+ *
+ * Hardware queues: the HIP runtime maps streams onto GPU_MAX_HW_QUEUES
+ * hardware queues (environment variable; 4 when unset) and two streams on one
+ * queue run one after the other.  walk_streams = 0 therefore resolves, when
+ * the pipeline is created, to min(TA_PIPELINE_WALK_STREAMS_DEFAULT, depth)
+ * only if GPU_MAX_HW_QUEUES (read then; unset counts as 4) is at least
+ * depth + w + 1 -- the fill streams, the walk streams and the caller's --
+ * and to 1 otherwise.  ta_pipeline_walk_streams returns the resolved count.
+ * ta_pipeline_create / _create_affine keep one walk stream whatever the
+ * environment.  The default is 1: on an MI355X two streams measured not
+ * steadily faster than one for 10,000 pairs of 1 kb and three slower (DESIGN
+ * 3.12), so the rule only matters to a build that defines another default.
+ */
+#ifndef TA_PIPELINE_WALK_STREAMS_DEFAULT
+#define TA_PIPELINE_WALK_STREAMS_DEFAULT 1u
+#endif
+typedef struct ta_pipeline_options {
+    uint32_t size;         /* sizeof(ta_pipeline_options) */
+    uint32_t walk_streams; /* 0: the default (above) */
+} ta_pipeline_options;
+int ta_pipeline_create_ex(ta_plan* const* slots, uint32_t depth, const ta_pipeline_options* options,
+                          ta_pipeline** out);
+uint32_t ta_pipeline_walk_streams(const ta_pipeline* pipe);
+
 /* Pack n_pairs CIGARs from their slots (device: cigar_slots, cigar_start,
  * cigar_len as written by an execution) back to back into dst (device):
  * pair p's bytes go to dst[dst_off[p] ..).  Enqueued on hip_stream.  For a
@@ -376,6 +413,9 @@ int ta_affine_plan_check(ta_affine_plan* plan);
 /* As ta_plan_context; and a ta_pipeline (above) whose slots are affine plans. */
 ta_context* ta_affine_plan_context(const ta_affine_plan* plan);
 int ta_pipeline_create_affine(ta_affine_plan* const* slots, uint32_t depth, ta_pipeline** out);
+/* As ta_pipeline_create_ex (its options, its walk-stream default and queue rule). */
+int ta_pipeline_create_affine_ex(ta_affine_plan* const* slots, uint32_t depth, const ta_pipeline_options* options,
+                                 ta_pipeline** out);
 /* As ta_plan_annotate, for an affine plan's execution. */
 int ta_affine_plan_annotate(ta_affine_plan* plan, const ta_device_io* io, const ta_annotate_io* out,
                             void* hip_stream);

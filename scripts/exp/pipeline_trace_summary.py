@@ -44,13 +44,36 @@ per_step = []
 for a, b in zip(fills, fills[1:]):
     back = next((x for x in backs if x[0] >= a[1] - 1000 and x[3] == a[3] and x[0] < a[1] + 2_000_000), None)
     walk = next((x for x in walks if x[0] >= a[1] - 1000), None)
-    fmt = next((x for x in fmts if walk and x[0] >= walk[1] - 1000), None)
+    fmt = next((x for x in fmts if walk and x[0] >= walk[1] - 1000 and x[3] == walk[3]), None)
     per_step.append({"fill": [us(a[0] - t0), us(a[1] - t0)], "fill_queue": a[3],
                      "hand_back": [us(back[0] - t0), us(back[1] - t0)] if back else None,
                      "walk": [us(walk[0] - t0), us(walk[1] - t0)] if walk else None,
                      "format": [us(fmt[0] - t0), us(fmt[1] - t0)] if fmt else None,
                      "next_fill_start_minus_fill_end_us": us(b[0] - a[1])})
 gaps = [b[0] - a[1] for a, b in zip(fills, fills[1:])]
+# the walks of consecutive steps (in start order) and each one's formatter (the next one on its queue):
+# how far walk k+1 reaches into walk k and into walk k's formatter, and the walk chain per step
+# (from one walk's start to the next one's), which is the period when the walks are what binds
+wk = inside(walks)
+wf = [next((x for x in fmts if x[0] >= w[1] - 1000 and x[3] == w[3]), None) for w in wk]
+pairs = [(a, fa, b) for a, fa, b in zip(wk, wf, wk[1:]) if fa]
+walk_chain = {
+    "walk_start_to_next_walk_start": stat([b[0] - a[0] for a, _, b in pairs]),
+    "next_walk_start_minus_walk_end": stat([b[0] - a[1] for a, _, b in pairs]),  # < 0: the walks overlap
+    "next_walk_start_minus_format_end": stat([b[0] - fa[1] for a, fa, b in pairs]),  # < 0: beside the formatter
+    "walks_overlapping_the_previous_walk": sum(b[0] < a[1] for a, _, b in pairs),
+    "walks_starting_before_the_previous_format_ends": sum(b[0] < fa[1] for a, fa, b in pairs),
+    "walk_plus_format": stat([fa[1] - a[0] for a, fa, _ in pairs]),
+    "format_start_minus_walk_end": stat([fa[0] - a[1] for a, fa, _ in pairs]),
+    "of": len(pairs)}
+# step by step over the whole trace (one fill, one hand-back launch and one walk per step, each kind in step
+# order): does a walk wait for its own step's hand-back launch?  (~0: it started when that launch ended)
+all_f, all_b, all_w = of("dual_fill_ck_kernel"), backs, sorted(walks, key=lambda x: x[1])
+if len(all_f) == len(all_b) == len(all_w):
+    own = list(zip(all_f, all_b, all_w))[-steps:]
+    walk_chain["walk_start_minus_own_hand_back_end"] = stat([w[0] - b[1] for _, b, w in own])
+    walk_chain["walk_start_minus_own_fill_end"] = stat([w[0] - f[1] for f, _, w in own])
+    walk_chain["walks_within_20us_of_own_hand_back_end"] = sum(0 <= w[0] - b[1] < 20_000 for _, b, w in own)
 out = {"trace": os.path.basename(os.path.dirname(os.path.abspath(sys.argv[1]))), "steps": len(per_step),
        "fill_queues": sorted({x[3] for x in fills}), "walk_queues": sorted({x[3] for x in inside(walks)}),
        "fill_blocks": fills[0][4], "hand_back_blocks": sorted({x[4] for x in inside(backs)}),
@@ -64,6 +87,7 @@ out = {"trace": os.path.basename(os.path.dirname(os.path.abspath(sys.argv[1]))),
        "gap_fill_end_to_next_fill_start": stat(gaps),
        "fills_overlapping_the_previous_fill": sum(g < 0 for g in gaps),
        "walk_start_minus_its_fill_end": stat([(p["walk"][0] - p["fill"][1]) * 1e3 for p in per_step if p["walk"]]),
+       "walk_chain": walk_chain,
        "per_step": per_step}
 json.dump(out, open(sys.argv[2], "w"), indent=1)
 print(json.dumps({a: b for a, b in out.items() if a != "per_step"}, indent=1))
