@@ -4,7 +4,8 @@ INFRASTRUCTURE ONLY -- only tests/ and the golden-vector scripts use it).
 * ``minimize``        -- team::KMER::Minimize (team_minimizers/
                          team_minimizers.cpp:122-225), entry for entry
 * ``first_occurrences`` -- remove_duplicates (team_mapper.cpp:26-42)
-* ``find_lis``        -- FindLIS (team_mapper.cpp:283-316)
+* ``find_lis``        -- FindLIS (team_mapper.cpp:283-316), numpy inner loop;
+                         ``find_lis_slow`` is the plain double loop
 * ``RefMapper``       -- ctypes over oracle/_ref/libref_mapper.so (the
                          reference's own Minimize compiled from source, and the
                          restated FindLIS), present only where it was built
@@ -92,7 +93,34 @@ def first_occurrences(mins):
 
 
 def find_lis(hits):
-    """FindLIS over [(fragment pos, reference pos)] -> chain list."""
+    """FindLIS over [(fragment pos, reference pos)] -> chain list.  The inner
+    loop of ``find_lis_slow`` as one numpy pass per i: the first j at the
+    strict maximum of lis[j] among the j that may precede i."""
+    n = len(hits)
+    if n == 0:
+        return []
+    a = np.asarray(hits, dtype=np.int64).reshape(-1, 2)
+    f, r = a[:, 0], a[:, 1]
+    lis = np.ones(n, dtype=np.int64)
+    prev = np.full(n, -1, dtype=np.int64)
+    for i in range(1, n):
+        ok = (r[i] > r[:i]) & (f[i] != f[:i]) & (((f[i] - f[:i]) & UINT_MAX) < 5000) & (
+            ((r[i] - r[:i]) & UINT_MAX) < 5000)
+        cand = np.where(ok, lis[:i], 0)
+        j = int(np.argmax(cand))  # first maximum
+        if cand[j] > 0:
+            lis[i] = cand[j] + 1
+            prev[i] = j
+    chain = []
+    i = int(np.argmax(lis))  # first maximal lis
+    while i >= 0:
+        chain.append(hits[i])
+        i = int(prev[i])
+    return [(int(x), int(y)) for x, y in chain[::-1]]
+
+
+def find_lis_slow(hits):
+    """FindLIS (team_mapper.cpp:283-316) as the reference writes it, loop for loop."""
     n = len(hits)
     if n == 0:
         return []

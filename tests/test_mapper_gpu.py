@@ -135,6 +135,106 @@ def test_mapper_slide17_published_lines():
     assert b"seq2\t7\t0\t5\t+\tref\t9\t3\t8\t18\t5\t60\tcg:Z:1M4D4I" in got
 
 
+def _edge_runs():
+    with open(os.path.join(MG, "edge_runs.json")) as f:
+        return json.load(f)["runs"]
+
+
+N_EDGE = 14
+TYPES = {"global": 0, "local": 1, "semiGlobal": 2}
+
+
+@pytest.mark.parametrize("run", range(N_EDGE))
+def test_mapper_cli_matches_reference_paf_edge(run):
+    """The edge family (make_mapper_golden.py EDGE_RUNS): strands, genome ends,
+    ties, gaps at the 5,000 limit, reads without hits, long hit lists."""
+    runs = _edge_runs()
+    assert len(runs) == N_EDGE
+    r = runs[run]
+    res = M.run_cli(r["args"] + [os.path.join(MG, r["genome"]), os.path.join(MG, r["reads"])], timeout=120)
+    assert res.returncode == 0, res.stderr.decode()
+    want = open(os.path.join(MG, r["paf"]), "rb").read()
+    got = res.stdout
+    if got != want:
+        gl, wl = got.splitlines(), want.splitlines()
+        diff = [(a[:160], b[:160]) for a, b in zip(gl, wl) if a != b][:3]
+        raise AssertionError(f"{r['paf']}: {len(gl)} vs {len(wl)} lines; first diffs {diff}")
+
+
+def _read_fastx(path):
+    """[(name, seq)] of a fixture written by make_mapper_golden.py (FASTA or 4-line FASTQ)."""
+    lines = open(path, "rb").read().split(b"\n")
+    if path.endswith(".fastq"):
+        return [(lines[i][1:].split()[0].decode(), lines[i + 1]) for i in range(0, len(lines) - 1, 4)]
+    out = []
+    for line in lines:
+        if line.startswith(b">"):
+            out.append([line[1:].split()[0].decode(), b""])
+        elif line:
+            out[-1][1] += line
+    return [(n, s) for n, s in out]
+
+
+def _options(args, fastq):
+    def val(flag, default, conv):
+        return conv(args[args.index(flag) + 1]) if flag in args else default
+
+    return dict(type=TYPES[val("-a", "global", str)], match=val("-m", 1, int), mismatch=val("-n", -1, int),
+                gap=val("-g", -1, int), k=val("-k", 15, int), w=val("-w", 5, int), f=val("-f", 0.001, float),
+                want_cigar="-c" in args, fastq_rules=fastq)
+
+
+def _check_result_against_paf(res, names, paf_path, glen, want_cigar):
+    """Every PAF column map_batch determines, read by read; reads without a
+    line are unmapped with all-zero coordinates."""
+    rows = {}
+    for line in open(paf_path, "rb").read().splitlines():
+        c = line.split(b"\t")
+        rows[c[0].decode()] = c
+    assert int(res.mapped.sum()) == len(rows)
+    for i, name in enumerate(names):
+        if name not in rows:
+            assert res.mapped[i] == 0, name
+            assert (res.q_begin[i], res.q_end[i], res.t_begin[i], res.t_end[i], res.scores[i]) == (0, 0, 0, 0, 0), name
+            continue
+        c = rows[name]
+        assert res.mapped[i] == 1, name
+        fwd = bool(res.strand_fwd[i])
+        assert c[4] == (b"+" if fwd else b"-"), name
+        assert (int(c[2]), int(c[3])) == (res.q_begin[i], res.q_end[i] + 1), name
+        tb, te = int(res.t_begin[i]), int(res.t_end[i])
+        # reverse-strand windows are reported in forward coordinates (team_mapper.cpp:686-697)
+        assert (int(c[7]), int(c[8])) == ((tb, te + 1) if fwd else (glen - te - 1, glen - tb)), name
+        assert int(c[9]) == res.scores[i], name
+        assert int(c[10]) == res.q_end[i] - res.q_begin[i] + 1, name
+        if want_cigar:
+            assert c[12] == b"cg:Z:" + res.cigar(i), name
+
+
+@pytest.mark.parametrize("run", range(N_EDGE))
+def test_map_batch_api_matches_reference_paf_edge(mp, run):
+    r = _edge_runs()[run]
+    gname, g = _read_fastx(os.path.join(MG, r["genome"]))[0]
+    reads = _read_fastx(os.path.join(MG, r["reads"]))
+    o = _options(r["args"], r["reads"].endswith(".fastq"))
+    idx = M.Index(mp, gname, g, o["k"], o["w"], o["f"])
+    res = idx.map_batch([s for _, s in reads], M.Options.make(**o))
+    _check_result_against_paf(res, [n for n, _ in reads], os.path.join(MG, r["paf"]), len(g), o["want_cigar"])
+    idx.close()
+
+
+@pytest.mark.parametrize("flag,value", [("-k", 16), ("-w", 65), ("-k", 0), ("-w", 0)])
+def test_k_and_w_outside_the_supported_range(mp, flag, value):
+    """kMaxK = 15, kMaxW = 64: the CLI exits non-zero with a message and prints
+    no PAF line; Index raises."""
+    r = _edge_runs()[0]
+    res = M.run_cli([flag, str(value), os.path.join(MG, r["genome"]), os.path.join(MG, r["reads"])], timeout=120)
+    assert res.returncode != 0 and res.stdout == b"" and b"unsupported k or w" in res.stderr
+    k, w = (value, 5) if flag == "-k" else (15, value)
+    with pytest.raises(RuntimeError, match="unsupported k or w"):
+        M.Index(mp, "g", b"ACGT" * 100, k, w, 0.001)
+
+
 def test_map_batch_api_matches_cli(mp):
     """The batched API (Index + map_batch) agrees with the CLI run on FASTQ rules."""
     r = _runs()[1]
@@ -148,6 +248,7 @@ def test_map_batch_api_matches_cli(mp):
     paf = open(os.path.join(MG, r["paf"]), "rb").read().splitlines()
     assert int(res.mapped.sum()) == len(paf)
     j = 0
+    strands = set()
     for i in range(len(reads)):
         if not res.mapped[i]:
             continue
@@ -156,3 +257,9 @@ def test_map_batch_api_matches_cli(mp):
         assert int(cols[2]) == res.q_begin[i] and int(cols[3]) == res.q_end[i] + 1
         assert int(cols[9]) == res.scores[i]
         assert cols[12] == b"cg:Z:" + res.cigar(i)
+        fwd = bool(res.strand_fwd[i])
+        strands.add(fwd)
+        assert cols[4] == (b"+" if fwd else b"-")
+        tb, te = int(res.t_begin[i]), int(res.t_end[i])
+        assert (int(cols[7]), int(cols[8])) == ((tb, te + 1) if fwd else (len(g) - te - 1, len(g) - tb))
+    assert strands == {True, False}
