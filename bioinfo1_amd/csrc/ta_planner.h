@@ -40,11 +40,25 @@ bool flex_ck_fits(int mode, uint32_t n, uint32_t m, int match, int mismatch, int
 // Every packed value of the affine dual fill (ta_affine.hip) within int16.
 bool affine_fits_int16(int mode, uint32_t n, uint32_t m, int ma, int mi, int open, int ext);
 
-// Linear-gap plan (team::Align scoring).
-struct Plan {
+// What the three plan families share, in name and meaning: the batch, the
+// visit order, and per pair the offsets of its codes and boundary row inside
+// its chunk (in the family's entries) and of its CIGAR slot (bytes).
+struct PlanBase {
     uint32_t n_pairs = 0;
-    int type = 0, match = 0, mismatch = 0, gap = 0;
+    int type = 0, match = 0, mismatch = 0;
     bool want_cigar = false;
+    std::vector<uint32_t> qlen, tlen;
+    std::vector<uint32_t> order;  // launch and traceback order (all pairs): the big ones start first
+    std::vector<uint64_t> ptr_off, bnd_off, slot_off;
+    uint64_t slots_bytes = 0;
+};
+struct ChunkSpan {  // a chunk's slice of `order`
+    uint32_t begin, count;
+};
+
+// Linear-gap plan (team::Align scoring).
+struct Plan : PlanBase {
+    int gap = 0;
     bool wide = false;   // local mode with |values| that could reach 2^25: unscaled int32 kernel
     bool fused = false;  // int32-only plans: the fill kernel walks its own pair
     bool end_aligned = true;  // pass tasks ticketed end-aligned (not kPlanPassMajor)
@@ -59,8 +73,6 @@ struct Plan {
     // dual fill leaves checkpoints instead of codes and the walk recomputes the
     // cells around its path (ta_layout.h ck_row_index, ta_walk_ck.hip)
     bool ck = false;
-    std::vector<uint32_t> qlen, tlen;
-    std::vector<uint32_t> order;    // traceback order (all pairs)
     std::vector<uint32_t> singles;  // int32 fill: pair ids
     std::vector<uint32_t> duals;    // equal-shape couples: 2 pair ids each
     std::vector<uint32_t> flexes;   // different-shape couples: 2 pair ids each
@@ -75,9 +87,7 @@ struct Plan {
     // ticket order (single << 32 | pass), pass-major.  Empty: no chunk is pipelined.
     std::vector<uint32_t> single_task_off;
     std::vector<uint64_t> single_tasks;
-    std::vector<uint64_t> ptr_off, bnd_off, slot_off;
-    struct Chunk {
-        uint32_t begin, count;    // all pairs (traceback order)
+    struct Chunk : ChunkSpan {
         uint32_t sbegin, scount;  // int32 fill: pairs
         uint32_t dbegin, dcount;  // dual fill: pair couples
         uint32_t fbegin, fcount;  // flexible dual fill: pair couples
@@ -88,7 +98,7 @@ struct Plan {
     };
     std::vector<Chunk> chunks;
     uint32_t n_dual_pairs = 0;  // pairs in packed couples (dual + flex)
-    uint64_t slots_bytes = 0, ws_ptr_dwords = 0, ws_bnd_words = 0;
+    uint64_t ws_ptr_dwords = 0, ws_bnd_words = 0;
 };
 
 // Plans n_pairs pairs; budget = bytes of 2-bit codes per chunk (> 0);
@@ -104,17 +114,11 @@ void build_plan(Plan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t
 uint64_t host_batch_code_bytes(uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, uint64_t bytes_per_entry);
 
 // Affine-gap plan (the extension of include/team_align_c.h).
-struct AffinePlan {
-    uint32_t n_pairs = 0;
-    int type = 0, match = 0, mismatch = 0, open = 0, extend = 0;
+struct AffinePlan : PlanBase {
+    int open = 0, extend = 0;
     bool end_aligned = true;  // pass tasks ticketed end-aligned (not kPlanPassMajor)
-    bool want_cigar = false;
-    std::vector<uint32_t> qlen, tlen;
-    std::vector<uint32_t> order;           // pairs by descending cells: the big ones start first
     std::vector<uint32_t> singles, duals;  // int32 fill: pairs; packed fill: 2 pair ids per couple
-    std::vector<uint64_t> ptr_off, bnd_off, slot_off;
-    struct Chunk {
-        uint32_t begin, count;    // plan order (traceback)
+    struct Chunk : ChunkSpan {
         uint32_t sbegin, scount;  // singles
         uint32_t dbegin, dcount;  // couples
         uint64_t ptr_entries, bnd_entries;
@@ -125,7 +129,7 @@ struct AffinePlan {
     // pipelined int32 fill of multi-pass singles, as Plan::single_task_off / single_tasks
     std::vector<uint32_t> single_task_off;
     std::vector<uint64_t> single_tasks;
-    uint64_t slots_bytes = 0, ws_ptr_entries = 0, ws_bnd_entries = 0;
+    uint64_t ws_ptr_entries = 0, ws_bnd_entries = 0;
 };
 
 // budget = bytes of 4-bit codes (8-byte entries) per chunk (> 0).
@@ -136,18 +140,14 @@ void build_affine_plan(AffinePlan& pl, uint32_t n_pairs, const uint32_t* qlen, c
 // Banded plan (the banded extension of include/team_align_c.h): pairs by
 // descending swept cells (the long ones start first), chunks closed when the
 // next pair's codes would pass the budget.
-struct BandPlan {
-    uint32_t n_pairs = 0;
-    int type = 0, match = 0, mismatch = 0, gap = 0;
-    bool want_cigar = false;
-    std::vector<uint32_t> qlen, tlen, band, order;
-    std::vector<uint64_t> ptr_off, bnd_off, slot_off;
-    struct Chunk {
-        uint32_t begin, count;
+struct BandPlan : PlanBase {
+    int gap = 0;
+    std::vector<uint32_t> band;  // per pair, clamped
+    struct Chunk : ChunkSpan {
         uint64_t ptr_dwords, bnd_words;
     };
     std::vector<Chunk> chunks;
-    uint64_t slots_bytes = 0, ws_ptr_dwords = 0, ws_bnd_words = 0;
+    uint64_t ws_ptr_dwords = 0, ws_bnd_words = 0;
     uint64_t band_cells = 0, swept_cells = 0;
 };
 

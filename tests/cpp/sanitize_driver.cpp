@@ -111,14 +111,81 @@ uint64_t splitmix(uint64_t& s) {
     return z ^ (z >> 31);
 }
 
+// What the three families' plans share (ta_planner.h PlanBase, ChunkSpan): `order` is a
+// permutation, the chunks tile it, every chunk lies within the workspace, every pair's
+// codes and boundary row lie inside its chunk, and the slot offsets add up.
+// chunk_codes(c) / chunk_bnd(c): a chunk's totals; pair_codes(x): the code entries pair x needs.
+template <class P, class ChunkCodes, class ChunkBnd, class PairCodes>
+void check_common(const P& pl, uint64_t ws_codes, uint64_t ws_bnd, ChunkCodes chunk_codes, ChunkBnd chunk_bnd,
+                  PairCodes pair_codes) {
+    const uint32_t N = pl.n_pairs;
+    std::vector<int> seen(N, 0);
+    for (uint32_t x : pl.order) {
+        CHECK(x < N);
+        if (x < N) ++seen[x];
+    }
+    for (uint32_t p = 0; p < N; ++p) CHECK(seen[p] == 1);
+    uint64_t count = 0;
+    for (const auto& c : pl.chunks) {
+        CHECK(c.begin == count && c.count > 0);
+        count += c.count;
+        CHECK(chunk_codes(c) <= ws_codes);
+        CHECK(chunk_bnd(c) <= ws_bnd);
+        for (uint32_t k = c.begin; k < c.begin + c.count && k < N; ++k) {
+            const uint32_t x = pl.order[k];
+            CHECK(pl.ptr_off[x] + (pl.want_cigar ? pair_codes(x) : 0) <= chunk_codes(c));
+            CHECK(pl.bnd_off[x] + ta::bnd_words(pl.qlen[x], pl.tlen[x]) <= chunk_bnd(c));
+        }
+    }
+    CHECK(count == N);
+    uint64_t so = 0;
+    for (uint32_t p = 0; p < N; ++p) {
+        CHECK(pl.slot_off[p] == so);
+        so += ta::cigar_slot_bytes(pl.qlen[p], pl.tlen[p]);
+    }
+    CHECK(so == pl.slots_bytes);
+}
+
+// Pipelined int32 tasks (linear and affine): every (single, pass) of a chunk with
+// spasses > 1 exactly once, a task's predecessor ticketed earlier; its pair holds
+// two record buffers of 4 entries per column.
+template <class P, class ChunkBnd>
+void check_single_tasks(const P& pl, ChunkBnd chunk_bnd) {
+    bool piped = false;
+    for (const auto& c : pl.chunks) piped |= c.spasses > 1;
+    CHECK(piped == !pl.single_task_off.empty());
+    if (!piped) return;
+    CHECK(pl.single_task_off.size() == pl.singles.size() + 1);
+    for (const auto& c : pl.chunks) {
+        if (c.spasses < 2) continue;
+        std::set<uint64_t> seen_tasks;
+        uint32_t maxp = 0;
+        for (uint32_t w = c.sbegin; w < c.sbegin + c.scount; ++w) {
+            const uint32_t x = pl.singles[w];
+            const uint32_t want = pl.qlen[x] && pl.tlen[x] ? ta::n_passes(pl.qlen[x]) : 0;
+            CHECK(pl.single_task_off[w + 1] - pl.single_task_off[w] == want);
+            maxp = std::max(maxp, want);
+            if (want > 1) CHECK(pl.bnd_off[x] + 4ull * (pl.tlen[x] + 1) <= chunk_bnd(c));
+        }
+        CHECK(maxp == c.spasses);
+        for (uint32_t k = pl.single_task_off[c.sbegin]; k < pl.single_task_off[c.sbegin + c.scount]; ++k) {
+            const uint64_t code = pl.single_tasks[k];
+            const uint32_t w = (uint32_t)(code >> 32), ps = (uint32_t)code;
+            CHECK(w >= c.sbegin && w < c.sbegin + c.scount);
+            if (ps) CHECK(seen_tasks.count(code - 1) == 1);  // predecessor ticketed earlier
+            if (w < pl.singles.size()) CHECK(ps < pl.single_task_off[w + 1] - pl.single_task_off[w]);
+            seen_tasks.insert(code);
+        }
+        CHECK(seen_tasks.size() == pl.single_task_off[c.sbegin + c.scount] - pl.single_task_off[c.sbegin]);
+    }
+}
+
 void check_linear(const ta::Plan& pl, uint64_t budget) {
     const uint32_t P = pl.n_pairs;
-    std::vector<int> seen(P, 0);
-    for (uint32_t x : pl.order) {
-        CHECK(x < P);
-        if (x < P) ++seen[x];
-    }
-    for (uint32_t p = 0; p < P; ++p) CHECK(seen[p] == 1);
+    const auto chunk_bnd = [](const ta::Plan::Chunk& c) { return c.bnd_words; };
+    check_common(
+        pl, pl.ws_ptr_dwords, pl.ws_bnd_words, [](const ta::Plan::Chunk& c) { return c.ptr_dwords; }, chunk_bnd,
+        [&](uint32_t x) { return ta::ptr_dwords_any(pl.qlen[x], pl.tlen[x], pl.blk); });
     // units partition the pairs: singles + duals + flex (a self-coupled flex pair counts once)
     std::vector<int> unit(P, 0);
     for (uint32_t x : pl.singles) ++unit[x];
@@ -131,26 +198,16 @@ void check_linear(const ta::Plan& pl, uint64_t budget) {
         if (pl.flexes[k + 1] != pl.flexes[k]) ++unit[pl.flexes[k + 1]];
     }
     for (uint32_t p = 0; p < P; ++p) CHECK(unit[p] == 1);
-    uint64_t count = 0, s = 0, d = 0, f = 0;
+    uint64_t s = 0, d = 0, f = 0;
     for (const auto& c : pl.chunks) {
-        CHECK(c.begin == count);
         CHECK(c.sbegin == s && c.dbegin == d && c.fbegin == f);
-        count += c.count;
         s += c.scount;
         d += c.dcount;
         f += c.fcount;
-        CHECK(c.ptr_dwords <= pl.ws_ptr_dwords);
-        CHECK(c.bnd_words <= pl.ws_bnd_words);
         // a chunk exceeds the budget only when it holds a single unit
         if (c.ptr_dwords * 4 > budget) CHECK(c.scount + c.dcount + c.fcount == 1);
-        for (uint32_t k = c.begin; k < c.begin + c.count; ++k) {
-            const uint32_t x = pl.order[k];
-            const uint64_t need = pl.want_cigar ? ta::ptr_dwords_any(pl.qlen[x], pl.tlen[x], pl.blk) : 0;
-            CHECK(pl.ptr_off[x] + need <= c.ptr_dwords);
-            CHECK(pl.bnd_off[x] + ta::bnd_words(pl.qlen[x], pl.tlen[x]) <= c.bnd_words);
-        }
     }
-    CHECK(count == P && s == pl.singles.size() && d * 2 == pl.duals.size() && f * 2 == pl.flexes.size());
+    CHECK(s == pl.singles.size() && d * 2 == pl.duals.size() && f * 2 == pl.flexes.size());
     // flex tasks: every (couple, pass) exactly once per chunk, pass-major
     CHECK(pl.flex_task_off.size() == pl.flexes.size() / 2 + 1);
     std::set<uint32_t> tasks(pl.flex_tasks.begin(), pl.flex_tasks.end());
@@ -165,35 +222,14 @@ void check_linear(const ta::Plan& pl, uint64_t budget) {
             CHECK(ps < pl.flex_task_off[w + 1] - pl.flex_task_off[w]);
         }
     }
-    // pipelined int32 tasks: every (single, pass) of a chunk with spasses > 1
-    // exactly once, pass-major; its pair holds two record buffers
-    bool piped = false;
-    for (const auto& c : pl.chunks) piped |= c.spasses > 1;
-    CHECK(piped == !pl.single_task_off.empty());
-    if (piped) {
-        CHECK(pl.single_task_off.size() == pl.singles.size() + 1);
+    check_single_tasks(pl, chunk_bnd);
+    // a pipelined plan is not fused, and its record regions are 8-byte aligned
+    for (const auto& c : pl.chunks) {
+        if (c.spasses < 2) continue;
         CHECK(!pl.fused);
-        for (const auto& c : pl.chunks) {
-            if (c.spasses < 2) continue;
-            std::set<uint64_t> seen_tasks;
-            uint32_t maxp = 0;
-            for (uint32_t w = c.sbegin; w < c.sbegin + c.scount; ++w) {
-                const uint32_t x = pl.singles[w];
-                const uint32_t want = pl.qlen[x] && pl.tlen[x] ? ta::n_passes(pl.qlen[x]) : 0;
-                CHECK(pl.single_task_off[w + 1] - pl.single_task_off[w] == want);
-                maxp = std::max(maxp, want);
-                if (want > 1) CHECK(pl.bnd_off[x] + 4ull * (pl.tlen[x] + 1) <= c.bnd_words && pl.bnd_off[x] % 2 == 0);
-            }
-            CHECK(maxp == c.spasses);
-            for (uint32_t k = pl.single_task_off[c.sbegin]; k < pl.single_task_off[c.sbegin + c.scount]; ++k) {
-                const uint64_t code = pl.single_tasks[k];
-                const uint32_t w = (uint32_t)(code >> 32), ps = (uint32_t)code;
-                CHECK(w >= c.sbegin && w < c.sbegin + c.scount);
-                if (ps) CHECK(seen_tasks.count(code - 1) == 1);  // predecessor ticketed earlier
-                if (w < pl.singles.size()) CHECK(ps < pl.single_task_off[w + 1] - pl.single_task_off[w]);
-                seen_tasks.insert(code);
-            }
-            CHECK(seen_tasks.size() == pl.single_task_off[c.sbegin + c.scount] - pl.single_task_off[c.sbegin]);
+        for (uint32_t w = c.sbegin; w < c.sbegin + c.scount; ++w) {
+            const uint32_t x = pl.singles[w];
+            if (pl.qlen[x] && pl.tlen[x] && ta::n_passes(pl.qlen[x]) > 1) CHECK(pl.bnd_off[x] % 2 == 0);
         }
     }
     for (size_t k = 0; k + 1 < pl.duals.size(); k += 2) {
@@ -202,84 +238,24 @@ void check_linear(const ta::Plan& pl, uint64_t budget) {
         CHECK(ta::n_passes(pl.qlen[pl.duals[k]]) < 64);  // hand-off tags epoch * 64 + pass + 1 (ta_dual.hip)
     }
     for (size_t k = 0; k + 1 < pl.flexes.size(); k += 2) CHECK(ta::n_passes(pl.qlen[pl.flexes[k]]) < 64);
-    uint64_t so = 0;
-    for (uint32_t p = 0; p < P; ++p) {
-        CHECK(pl.slot_off[p] == so);
-        so += ta::cigar_slot_bytes(pl.qlen[p], pl.tlen[p]);
-    }
-    CHECK(so == pl.slots_bytes);
 }
 
 void check_affine(const ta::AffinePlan& pl) {
-    const uint32_t P = pl.n_pairs;
-    std::vector<int> seen(P, 0);
-    for (uint32_t x : pl.order)
-        if (x < P) ++seen[x];
-    for (uint32_t p = 0; p < P; ++p) CHECK(seen[p] == 1);
-    uint64_t count = 0;
-    for (const auto& c : pl.chunks) {
-        CHECK(c.begin == count);
-        count += c.count;
-        CHECK(c.ptr_entries <= pl.ws_ptr_entries);
-    }
-    CHECK(count == P);
+    const auto chunk_bnd = [](const ta::AffinePlan::Chunk& c) { return c.bnd_entries; };
+    check_common(
+        pl, pl.ws_ptr_entries, pl.ws_bnd_entries, [](const ta::AffinePlan::Chunk& c) { return c.ptr_entries; }, chunk_bnd,
+        [&](uint32_t x) { return ta::ptr_dwords(pl.qlen[x], pl.tlen[x]); });
     for (size_t k = 0; k + 1 < pl.duals.size(); k += 2) CHECK(ta::n_passes(pl.qlen[pl.duals[k]]) < 64);
-    bool piped = false;
-    for (const auto& c : pl.chunks) piped |= c.spasses > 1;
-    CHECK(piped == !pl.single_task_off.empty());
-    if (piped) {
-        CHECK(pl.single_task_off.size() == pl.singles.size() + 1);
-        for (const auto& c : pl.chunks) {
-            if (c.spasses < 2) continue;
-            std::set<uint64_t> seen_tasks;
-            for (uint32_t w = c.sbegin; w < c.sbegin + c.scount; ++w) {
-                const uint32_t x = pl.singles[w];
-                if (ta::n_passes(pl.qlen[x]) > 1 && pl.tlen[x])
-                    CHECK(pl.bnd_off[x] + 4ull * (pl.tlen[x] + 1) <= c.bnd_entries);
-            }
-            for (uint32_t k = pl.single_task_off[c.sbegin]; k < pl.single_task_off[c.sbegin + c.scount]; ++k) {
-                const uint32_t w = (uint32_t)(pl.single_tasks[k] >> 32), ps = (uint32_t)pl.single_tasks[k];
-                CHECK(w >= c.sbegin && w < c.sbegin + c.scount);
-                if (ps) CHECK(seen_tasks.count(pl.single_tasks[k] - 1) == 1);  // predecessor ticketed earlier
-                if (w < pl.singles.size()) CHECK(ps < pl.single_task_off[w + 1] - pl.single_task_off[w]);
-                seen_tasks.insert(pl.single_tasks[k]);
-            }
-            CHECK(seen_tasks.size() == pl.single_task_off[c.sbegin + c.scount] - pl.single_task_off[c.sbegin]);
-        }
-    }
+    check_single_tasks(pl, chunk_bnd);
 }
 
 void check_band(const ta::BandPlan& pl, uint32_t width) {
-    const uint32_t P = pl.n_pairs;
-    std::vector<int> seen(P, 0);
-    for (uint32_t x : pl.order) {
-        CHECK(x < P);
-        if (x < P) ++seen[x];
-    }
-    for (uint32_t p = 0; p < P; ++p) {
-        CHECK(seen[p] == 1);
+    check_common(
+        pl, pl.ws_ptr_dwords, pl.ws_bnd_words, [](const ta::BandPlan::Chunk& c) { return c.ptr_dwords; },
+        [](const ta::BandPlan::Chunk& c) { return c.bnd_words; },
+        [&](uint32_t x) { return ta::band_ptr_dwords(pl.qlen[x], pl.tlen[x], pl.band[x]); });
+    for (uint32_t p = 0; p < pl.n_pairs; ++p)
         CHECK(pl.band[p] == ta::band_clamp(pl.qlen[p], pl.tlen[p], width) && pl.band[p] <= width);
-    }
-    uint64_t count = 0;
-    for (const auto& c : pl.chunks) {  // chunks tile the order
-        CHECK(c.begin == count && c.count > 0);
-        count += c.count;
-        CHECK(c.ptr_dwords <= pl.ws_ptr_dwords);
-        CHECK(c.bnd_words <= pl.ws_bnd_words);
-        for (uint32_t k = c.begin; k < c.begin + c.count && k < P; ++k) {
-            const uint32_t x = pl.order[k];
-            const uint64_t need = pl.want_cigar ? ta::band_ptr_dwords(pl.qlen[x], pl.tlen[x], pl.band[x]) : 0;
-            CHECK(pl.ptr_off[x] + need <= c.ptr_dwords);
-            CHECK(pl.bnd_off[x] + ta::bnd_words(pl.qlen[x], pl.tlen[x]) <= c.bnd_words);
-        }
-    }
-    CHECK(count == P);
-    uint64_t so = 0;
-    for (uint32_t p = 0; p < P; ++p) {
-        CHECK(pl.slot_off[p] == so);
-        so += ta::cigar_slot_bytes(pl.qlen[p], pl.tlen[p]);
-    }
-    CHECK(so == pl.slots_bytes);
 }
 
 constexpr uint32_t kBandWidths[] = {0, 1, 37, 5000};  // (5000 clamps on most shapes below)
