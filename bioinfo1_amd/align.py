@@ -153,6 +153,27 @@ def lib() -> C.CDLL:
     L.ta_banded_plan_execute_traceback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.ta_banded_plan_check.argtypes = [C.c_void_p]
     L.ta_banded_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # banded affine extension (include/team_align_c.h, no reference counterpart)
+    L.ta_align_batch_banded_affine.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64p, u32p, C.c_void_p, u64p, u32p,
+                                               u32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, u32p,
+                                               C.c_void_p, C.c_uint64, u64p, u32p]
+    L.ta_banded_affine_plan_create.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, u32p, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
+                                               C.POINTER(C.c_void_p)]
+    L.ta_banded_affine_plan_destroy.argtypes = [C.c_void_p]
+    L.ta_banded_affine_plan_destroy.restype = None
+    for f in ("ta_banded_affine_plan_cigar_slots_bytes", "ta_banded_affine_plan_workspace_bytes",
+              "ta_banded_affine_plan_band_cells", "ta_banded_affine_plan_swept_cells"):
+        getattr(L, f).restype = C.c_uint64
+        getattr(L, f).argtypes = [C.c_void_p]
+    L.ta_banded_affine_plan_chunks.restype = C.c_uint32
+    L.ta_banded_affine_plan_chunks.argtypes = [C.c_void_p]
+    L.ta_banded_affine_plan_pair_chunks.argtypes = [C.c_void_p, u32p]
+    L.ta_banded_affine_plan_execute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ta_banded_affine_plan_execute_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ta_banded_affine_plan_execute_traceback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ta_banded_affine_plan_check.argtypes = [C.c_void_p]
+    L.ta_banded_affine_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # the annotate post-pass (info records, =/X CIGARs)
     L.ta_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ta_affine_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -196,6 +217,9 @@ BANDED_ABI_SYMBOLS = [
     "ta_banded_plan_annotate", "ta_align_batch_banded",
 ]
 ABI_SYMBOLS += BANDED_ABI_SYMBOLS
+# The banded affine extension's symbols (checked by tests/test_banded_affine_ref.py).
+BANDED_AFFINE_ABI_SYMBOLS = [s.replace("banded", "banded_affine") for s in BANDED_ABI_SYMBOLS]
+ABI_SYMBOLS += BANDED_AFFINE_ABI_SYMBOLS
 # The drop-in C++ entry point (team_alignment.hpp), g++/libstdc++ cxx11 mangling.
 TEAM_ALIGN_SYMBOL = ("_ZN4team5AlignEPKcjS1_jNS_13AlignmentTypeEiiiPNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEEPj")
 
@@ -302,6 +326,16 @@ class Aligner:
         return self._batch(batch, type, (match, mismatch, gap), want_cigar, affine=False,
                            band=_band_array(band, batch.n_pairs))
 
+    def align_batch_banded_affine(self, batch, type, match: int, mismatch: int, gap_open: int, gap_extend: int, band,
+                                  want_cigar: bool = True) -> BatchResult:
+        """The banded affine extension (ta_align_batch_banded_affine): the
+        affine-gap extension over the cells of the banded extension's band.
+        band: an int or one per pair.  gap_open == 0 gives exactly
+        align_batch_banded with gap = gap_extend; a band >= max(n, m) exactly
+        align_batch_affine."""
+        return self._batch(batch, type, (match, mismatch, gap_open, gap_extend), want_cigar, affine=True,
+                           band=_band_array(band, batch.n_pairs))
+
     def _batch(self, batch, type, scoring, want_cigar, affine, band=None) -> BatchResult:
         L = lib()
         t = _check_type(type)
@@ -320,7 +354,7 @@ class Aligner:
         fn = L.ta_align_batch_affine if affine else L.ta_align_batch
         extra = ()
         if band is not None:
-            fn = L.ta_align_batch_banded
+            fn = L.ta_align_batch_banded_affine if affine else L.ta_align_batch_banded
             extra = (_p(band if band.size else np.zeros(1, np.uint32), C.c_uint32),)
         r = fn(
             self._h, P, qb.ctypes.data, _p(batch.qoff, C.c_uint64), _p(batch.qlen, C.c_uint32), tbb.ctypes.data,
@@ -371,6 +405,17 @@ def align_banded(query: bytes, target: bytes, type, match: int, mismatch: int, g
     _check_type(type)
     res = default_aligner().align_batch_banded(from_pairs([(bytes(query), bytes(target))]), type, match, mismatch,
                                                gap, band, want_cigar)
+    return int(res.scores[0]), res.cigar(0), int(res.target_begins[0])
+
+
+def align_banded_affine(query: bytes, target: bytes, type, match: int, mismatch: int, gap_open: int, gap_extend: int,
+                        band: int, want_cigar: bool = True):
+    """The banded affine extension for one pair -> (score, cigar bytes or None, target_begin)."""
+    from .synth import from_pairs
+
+    _check_type(type)
+    res = default_aligner().align_batch_banded_affine(from_pairs([(bytes(query), bytes(target))]), type, match,
+                                                      mismatch, gap_open, gap_extend, band, want_cigar)
     return int(res.scores[0]), res.cigar(0), int(res.target_begins[0])
 
 
@@ -507,7 +552,8 @@ class DevicePlan:
     current torch stream (asynchronous)."""
 
     def __init__(self, aligner: Aligner, batch, type, match, mismatch, gap, want_cigar=True, device=None,
-                 workspace_budget: int = 0, gap_open=None, flags: int = 0, inputs=None, records=None, band=None):
+                 workspace_budget: int = 0, gap_open=None, flags: int = 0, inputs=None, records=None, band=None,
+                 _banded_affine: bool = False):
         """gap_open=None: team::Align's linear gap.  gap_open=o: the affine-gap
         extension (ta_affine_plan_*) with gap_extend = gap.  flags: TA_PLAN_*
         kernel selection (tests / measurements; same results).  inputs: the
@@ -516,11 +562,13 @@ class DevicePlan:
         records: an int32 device tensor of >= 3 * P entries that receives the
         scores, target_begins and CIGAR lengths back to back (one download).
         band=None: the whole matrix.  band=w (an int, or one per pair): the
-        banded extension (ta_banded_plan_*); not together with gap_open."""
+        banded extension (ta_banded_plan_*); not together with gap_open --
+        the banded affine extension is DevicePlan.banded_affine(...)."""
         import torch
 
-        if band is not None and gap_open is not None:
-            raise ValueError("band and gap_open cannot be combined: the banded extension is linear-gap only")
+        if band is not None and gap_open is not None and not _banded_affine:
+            raise ValueError("band and gap_open cannot be combined here: the banded extension is linear-gap only; "
+                             "use DevicePlan.banded_affine(...) for the banded affine extension")
         L = lib()
         t = _check_type(type)
         self.torch = torch
@@ -529,7 +577,8 @@ class DevicePlan:
         self.want_cigar = bool(want_cigar)
         self.affine = gap_open is not None
         self.banded = band is not None
-        family = "ta_affine_plan_" if self.affine else "ta_banded_plan_" if self.banded else "ta_plan_"
+        family = ("ta_banded_affine_plan_" if self.affine and self.banded else
+                  "ta_affine_plan_" if self.affine else "ta_banded_plan_" if self.banded else "ta_plan_")
         self._fn = lambda name: getattr(L, name.replace("ta_plan_", family))
         h = C.c_void_p()
         scoring = (match, mismatch, gap_open, gap) if self.affine else (match, mismatch, gap)
@@ -570,13 +619,22 @@ class DevicePlan:
         self.workspace_bytes = int(self._fn("ta_plan_workspace_bytes")(h))
         self.chunks = int(self._fn("ta_plan_chunks")(h))
         linear = not (self.affine or self.banded)
-        self.dual_pairs = (int(L.ta_affine_plan_dual_pairs(h)) if self.affine else
-                           0 if self.banded else int(L.ta_plan_dual_pairs(h)))
+        self.dual_pairs = (0 if self.banded else int(L.ta_affine_plan_dual_pairs(h)) if self.affine else
+                           int(L.ta_plan_dual_pairs(h)))
         self.flex_pairs = int(L.ta_plan_flex_pairs(h)) if linear else 0
         self.fused = bool(L.ta_plan_fused(h)) if linear else False
         w = int(L.ta_plan_walk(h)) if linear else -1
         self.walk, self.blk, self.ck = (w & 0xFF, bool(w & 0x100), bool(w & 0x200)) if w >= 0 else (None, False, False)
         self.aligner = aligner
+
+    @classmethod
+    def banded_affine(cls, aligner: Aligner, batch, type, match, mismatch, gap_open, gap_extend, band,
+                      want_cigar=True, device=None, workspace_budget: int = 0, inputs=None, records=None):
+        """A plan of the banded affine extension (ta_banded_affine_plan_*):
+        affine gaps over the cells of the band.  band: an int, or one per
+        pair.  The other arguments as the constructor's."""
+        return cls(aligner, batch, type, match, mismatch, gap_extend, want_cigar, device, workspace_budget,
+                   gap_open=gap_open, inputs=inputs, records=records, band=band, _banded_affine=True)
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
@@ -586,14 +644,14 @@ class DevicePlan:
         """Banded plans: the in-band interior cells of all pairs (ta_banded_plan_band_cells)."""
         if not self.banded:
             raise AttributeError("band_cells: not a banded plan")
-        return int(lib().ta_banded_plan_band_cells(self._h))
+        return int(self._fn("ta_plan_band_cells")(self._h))
 
     @property
     def swept_cells(self) -> int:
         """Banded plans: the cells the kernels sweep (ta_banded_plan_swept_cells)."""
         if not self.banded:
             raise AttributeError("swept_cells: not a banded plan")
-        return int(lib().ta_banded_plan_swept_cells(self._h))
+        return int(self._fn("ta_plan_swept_cells")(self._h))
 
     def set_inputs(self, inputs):
         """Point the plan at another batch of the same shapes already in HBM:

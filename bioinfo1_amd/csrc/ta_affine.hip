@@ -27,7 +27,8 @@
 // bottom row's (H, F) to the next pass through a boundary row in HBM.
 // The traceback walks the three-state machine one cell per iteration on the
 // SALU with a 64-step tile of the lane stripe's codes held in two VGPRs, and
-// writes runs through the shared RunWriter (ta_device.h).
+// writes runs through the shared RunWriter (ta_device.h); the walk itself is
+// shared with the banded affine plan (ta_walk_affine.h).
 #include <hip/hip_runtime.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
 
@@ -44,6 +45,7 @@
 #include "ta_plan_driver.h"
 #include "ta_planner.h"
 #include "ta_packed.h"
+#include "ta_walk_affine.h"
 
 namespace ta {
 namespace {
@@ -498,95 +500,7 @@ __global__ void affine_fill_combine_kernel(AffArgs a) {
     a.goal_j[p] = gj;
 }
 
-// The three-state walk (oracle/affine_oracle.c): H-state follows the source
-// code, E/F-state emits one I/D per cell and keeps going while the cell's
-// extension bit is set.  One cell per iteration; the wave holds the codes of
-// 64 consecutive steps of the current lane stripe (lane k: step tt0 + k).
-template <int MODE>
-__device__ __forceinline__ void aff_traceback_pair(const uint2* P, uint32_t n, uint32_t m, uint32_t gi, uint32_t gj,
-                                                   char* slot, uint64_t cap, int lane, uint64_t* start_in_slot,
-                                                   uint32_t* len) {
-    RunWriter w{slot + cap, 0u, 0u, 0u, 0u, 0u, 0u, lane};
-    if (MODE == kSemi && (gj != m || gi != n)) {  // :306-315 (the walk runs backwards: pushed first)
-        if (gi == n) {
-            if (m - gj) w.push('I', m - gj);
-        } else if (gj == m && n - gi) {
-            w.push('D', n - gi);
-        }
-    }
-    const uint32_t Tmax = pass_steps(m);
-    uint32_t i = gi, j = gj, state = 0;  // 0 H, 1 E, 2 F
-    uint32_t tP = 0xFFFFFFFFu, tL = 0xFFFFFFFFu, tt0 = 0;
-    uint32_t cx = 0, cy = 0;
-    // every iteration moves or leaves H-state, so 2(n+m)+2 bounds a correct
-    // walk; the bound (and the E/F edge checks) only keep a corrupt code from
-    // spinning the wave
-    for (uint32_t it = 0; it < 2u * (n + m) + 2u; ++it) {
-        if ((state == 1 && j == 0) || (state == 2 && i == 0)) break;
-        if (state == 0) {
-            if (MODE == kLocal) {
-                if (min(i, j) == 0) break;  // boundary cost 0 ends the walk (:202)
-            } else {
-                if (i == 0) {  // row 0: INSERT run (:89-92)
-                    if (j) w.push('I', j);
-                    break;
-                }
-                if (j == 0) {  // column 0: DELETE run (:83-86)
-                    w.push('D', i);
-                    break;
-                }
-            }
-        }
-        const uint32_t row = i - 1;
-        const uint32_t ln = (row >> 4) & 63u, r = row & 15u, ps = row >> 10;
-        const uint32_t t = (j - 1) + ln;
-        if (ps != tP || ln != tL || t < tt0) {
-            tP = ps;
-            tL = ln;
-            tt0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(max(t, 63u) - 63u));
-            const uint32_t ts = tt0 + (uint32_t)lane;
-            cx = cy = 0;
-            if (ts < Tmax) {
-                const uint2 v = P[((uint64_t)tP * Tmax + ts) * kWave + tL];
-                cx = v.x;
-                cy = v.y;
-            }
-        }
-        const uint32_t kk = t - tt0;
-        const uint32_t sh = 15u - r;
-        const uint32_t x = (uint32_t)rdlane((int)cx, kk) >> sh, y = (uint32_t)rdlane((int)cy, kk) >> sh;
-        if (state == 0) {
-            const uint32_t dflag = (x >> 16) & 1u, iflag = x & 1u;
-            if (MODE == kLocal && (dflag & iflag)) break;  // STOP: cost == 0 (:202)
-            if (dflag) {
-                state = 2;
-            } else if (iflag) {
-                state = 1;
-            } else {
-                // a whole M run at once: lane L holds step tt0 + L of this stripe, i.e. the
-                // diagonal cell d = kk - L back (row r - d); the streak of M codes going down
-                // from lane kk is the run (capped at the stripe's first row and the borders)
-                const uint32_t v = (cx >> ((sh + (kk - (uint32_t)lane)) & 31u)) & 0x10001u;
-                const uint32_t run = min(streak_down(ballot(v == 0u), kk), min(min(i, j), r + 1u));
-                w.push('M', run);
-                i -= run;
-                j -= run;
-            }
-        } else if (state == 1) {
-            w.push('I', 1);
-            --j;
-            state = (y & 1u) ? 1u : 0u;
-        } else {
-            w.push('D', 1);
-            --i;
-            state = ((y >> 16) & 1u) ? 2u : 0u;
-        }
-    }
-    w.finish();
-    *start_in_slot = cap - w.used;
-    *len = w.used;
-}
-
+// The three-state walk is ta_walk_affine.h aff_traceback_pair, here over the whole matrix's codes.
 template <int MODE>
 __global__ __launch_bounds__(kBlock) void affine_traceback_kernel(AffArgs a) {
     const int lane = threadIdx.x & 63;
@@ -599,8 +513,8 @@ __global__ __launch_bounds__(kBlock) void affine_traceback_kernel(AffArgs a) {
     const uint32_t gj = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.goal_j[p]);
     uint64_t st;
     uint32_t len;
-    aff_traceback_pair<MODE>(a.ptrs + a.ptr_off[p], n, m, gi, gj, a.slots + a.slot_off[p], cigar_slot_bytes(n, m),
-                             lane, &st, &len);
+    aff_traceback_pair<MODE>(a.ptrs + a.ptr_off[p], AffFullGeo{pass_steps(m)}, n, m, gi, gj, a.slots + a.slot_off[p],
+                             cigar_slot_bytes(n, m), lane, &st, &len);
     if (lane == 0) {
         a.cigar_start[p] = a.slot_off[p] + st;
         a.cigar_len[p] = len;

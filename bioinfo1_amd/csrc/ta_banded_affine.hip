@@ -1,0 +1,612 @@
+// bioinfo1_amd/csrc/ta_banded_affine.hip -- the banded affine extension on
+// gfx950: affine-gap fill and traceback kernels that compute only the cells
+// within a per-pair band of diagonals, and the ta_banded_affine_plan host
+// driver of include/team_align_c.h.
+//
+// Neither the reference nor the two oracles have a counterpart; the semantics
+// are DEFINED in include/team_align_c.h (and restated in
+// tests/banded_affine_ref.py): oracle/affine_oracle.c's Gotoh H/E/F, tie
+// order, goals, three-state walk and CIGAR format with the cells outside
+// lo <= j - i <= hi not existing.  gap_open == 0 gives the linear banded
+// extension's results, a band that holds every cell the affine extension's.
+//
+// Layout.  The cell update is the int32 affine pass
+// (ta_affine.hip aff_pass) inside the banded pass's geometry (ta_banded.hip
+// band_pass): one wave64 per pair, lane l owns 16 query rows of a 1024-row
+// pass, one-step lane skew, DPP wave_shr:1 hand-off of the last row's H and F,
+// the pass's bottom row (H, F) through an int2 boundary row in HBM.  Pass p
+// sweeps only the columns c0 .. c1 that hold an in-band cell of its rows; the
+// step loop is split at the closed-form bounds between which every lane's
+// whole stripe is in band (the unmasked cell update).
+//   * Inside the swept rectangle the cells off the band get H, E and F forced
+//     to kSent after the local clamp and before the argmax, the goal scans
+//     and the boundary store.  |values| < 2^26 (the range rule) and kSent =
+//     -2^29, so a candidate formed from kSent plus one step is below every
+//     real value: it never wins and never ties.  An in-band cell's H is always
+//     real (its diagonal predecessor is in band), so such a candidate is never
+//     carried further than the one cell next to the band's edge.
+//   * Codes: four 16-row bit planes per step as one uint2 per (pass, swept
+//     step, lane), .x = D << 16 | I, .y = F-ext << 16 | E-ext, exactly
+//     affine_fill_kernel's; the entry index is the linear band's
+//     (band_pass_offset), counted in 8-byte entries.
+//   * The E-ext (F-ext) bit of an in-band cell whose left (upper) neighbour is
+//     out of band compares two candidates formed from kSent and may differ
+//     from the definition's 0.  The walk is in E (F) state at a cell only when
+//     that cell's E (F) won or extended a winning gap, i.e. is real, which
+//     needs the left (upper) neighbour in band: such a bit is never read.
+// The walk is the affine three-state walk (ta_walk_affine.h) over that layout.
+#include <hip/hip_runtime.h>
+#include <rocprofiler-sdk-roctx/roctx.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/team_align_c.h"
+#include "ta_context.h"
+#include "ta_device.h"
+#include "ta_host_batch.h"
+#include "ta_plan_driver.h"
+#include "ta_planner.h"
+#include "ta_walk_affine.h"
+
+namespace ta {
+namespace {
+
+constexpr int kSent = -(1 << 29);   // an out-of-band cell's H, E and F; E(i,0), F(0,j)
+constexpr int kFloor = -(1 << 26);  // below every real value, above every value formed from kSent
+
+struct BandAffArgs {
+    const uint32_t* order;  // plan order; this launch handles order[begin .. begin+count)
+    uint32_t begin, count;
+    const uint8_t* qbytes;
+    const uint64_t* qoff;
+    const uint32_t* qlen;
+    const uint8_t* tbytes;
+    const uint64_t* toff;
+    const uint32_t* tlen;
+    const uint32_t* band;  // per pair, clamped (band_clamp)
+    int match, mismatch, open, extend;
+    uint2* ptrs;              // chunk workspace, one uint2 per (pass, swept step, lane)
+    const uint64_t* ptr_off;  // per pair, uint2 entries from ptrs
+    int2* bnd;                // chunk pass-boundary rows: (H, F) per column
+    const uint64_t* bnd_off;  // per pair, int2 entries from bnd
+    int32_t* score;
+    uint32_t* target_begin;
+    uint32_t* goal_i;
+    uint32_t* goal_j;
+    char* slots;
+    const uint64_t* slot_off;
+    uint64_t* cigar_start;
+    uint32_t* cigar_len;
+};
+
+// One pass = rows row_base+1 .. row_base+nrows against the columns c0 .. c1.
+//   QDASH  some query row of this pass is '-' (its vertical gap steps are free)
+template <int MODE, bool CIGAR, bool QDASH>
+__device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uint8_t* Q, const uint8_t* T, uint32_t n,
+                                                 uint32_t m, uint32_t w, uint32_t pass, bool last_pass, uint2* prow,
+                                                 int2* B, int lane) {
+    constexpr int R = kRows;
+    const int O = a.open, X = a.extend, OX = wadd(a.open, a.extend);
+    const int MA = a.match, MI = a.mismatch;
+    const int lo = band_lo(n, m, w), hi = band_hi(n, m, w);
+    const uint32_t BW = (uint32_t)(hi - lo);
+    const uint32_t row_base = pass * kPassRows;
+    const uint32_t nrows = min((uint32_t)kPassRows, n - row_base);
+    const uint32_t nl = (nrows + R - 1) / R;   // lanes in use
+    const uint32_t nv = nrows - (nl - 1) * R;  // valid rows of lane nl-1
+    const uint32_t vlim = (uint32_t)lane < nl - 1 ? R : ((uint32_t)lane == nl - 1 ? nv : 0u);
+    const bool has_next = !last_pass;
+    const uint32_t c0 = band_c0(n, m, w, pass), c1 = band_c1(n, m, w, pass);
+    const uint32_t ncols = c1 - c0 + 1;
+    const uint32_t steps = ncols + nl - 1;
+    const uint8_t* Tc = T + (c0 - 1);  // the byte of column c0 + k is Tc[k]
+    auto in_band = [&](int d) { return (uint32_t)(d - lo) <= BW; };
+    // H of a boundary cell (row 0 or column 0) L steps from (0, 0), where in band
+    auto edge = [&](uint32_t L) { return (MODE == kGlobal && L) ? wadd(O, wmul(L, X)) : 0; };
+
+    uint32_t qp[R / 4];  // the lane's 16 query bytes, 4 per register
+#pragma unroll
+    for (int k = 0; k < R / 4; ++k) {
+        uint32_t x = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const uint32_t i0 = row_base + (uint32_t)lane * R + 4 * k + b;
+            x |= (i0 < n ? (uint32_t)Q[i0] : 0u) << (8 * b);
+        }
+        qp[k] = x;
+    }
+    auto qbyte = [&](int r) { return (qp[r >> 2] >> (8 * (r & 3))) & 0xFFu; };
+    // column c0 - 1: the boundary column 0 where in band, else nothing; E(i, 0) never exists
+    int H[R], E[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint32_t i = row_base + (uint32_t)lane * R + r + 1;
+        H[r] = (c0 == 1 && in_band(-(int)i)) ? edge(i) : kSent;
+        E[r] = kSent;
+    }
+    // per-row vertical gap constants ('-' rows are free)
+    int goq[R], geq[R];
+    if constexpr (QDASH) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const bool d = qbyte(r) == (uint32_t)'-';
+            goq[r] = d ? 0 : OX;
+            geq[r] = d ? 0 : X;
+        }
+    }
+    const uint32_t i_above = row_base + (uint32_t)lane * R;  // the row above the stripe, at column c0 - 1
+    int recvH = kSent;
+    if (in_band((int)(c0 - 1) - (int)i_above)) {
+        if (c0 == 1) recvH = edge(i_above);
+        else if (lane == 0) recvH = B[c0 - 1].x;  // (c0 > 1 only below pass 0: the previous pass's bottom row)
+    }
+    int recvF = kSent, Flast = kSent;
+    int kc[R];  // local argmax key = 16 h + (15 - r) on valid rows
+    if constexpr (MODE == kLocal) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) kc[r] = (uint32_t)r < vlim ? (R - 1 - r) : -(1 << 30);
+    }
+    int tc = 0;
+    int bestkey = INT_MIN;
+    uint32_t bestj = 0;
+    int rowbest = kFloor;
+    uint32_t rowbest_j = 0;
+
+    // the previous pass's bottom row, 64 columns c0 + 64 k + lane per chunk; what it did
+    // not sweep (beyond its c1) is out of band in that row, and so is never read
+    auto load_top = [&](uint32_t k) {
+        const uint32_t j = c0 + k * 64u + (uint32_t)lane;
+        return (j <= m && in_band((int)j - (int)row_base)) ? B[j] : make_int2(kSent, kSent);
+    };
+    uint32_t tcur = load_tchunk(Tc, ncols, 0, lane), tnext = load_tchunk(Tc, ncols, 1, lane);
+    int2 bcur = make_int2(kSent, kSent), bnext = bcur;
+    if (pass > 0) {
+        bcur = load_top(0);
+        bnext = load_top(1);
+    }
+    // e - r = (j - i) - lo of the lane's row r at the coming step
+    int e = (int)c0 - (int)row_base - 1 - 17 * lane - lo;
+
+    auto step = [&](uint32_t t, auto masked_tag) {
+        constexpr bool MASKED = decltype(masked_tag)::value;
+        if ((t & 255u) == 0 && t) {
+            tcur = tnext;
+            tnext = load_tchunk(Tc, ncols, (t >> 8) + 1, lane);
+        }
+        int topH, topF;
+        if (pass == 0) {  // row 0 where in band; F(0, j) never exists
+            topH = (int)(c0 + t) <= hi ? edge(c0 + t) : kSent;
+            topF = kSent;
+        } else {
+            if ((t & 63u) == 0 && t) {
+                bcur = bnext;
+                bnext = load_top((t >> 6) + 1);
+            }
+            topH = rdlane(bcur.x, t & 63u);
+            topF = rdlane(bcur.y, t & 63u);
+        }
+        const uint32_t word = (uint32_t)rdlane((int)tcur, (t >> 2) & 63u);
+        const int newc = (int)((word >> ((t & 3u) * 8)) & 0xFFu);
+        const int prev = recvH;
+        recvH = wave_shr1(topH, H[R - 1]);
+        recvF = wave_shr1(topF, Flast);
+        tc = wave_shr1(newc, tc);
+
+        const uint32_t jrel = t - (uint32_t)lane;  // column c0 + jrel
+        const bool active = !MASKED || (((uint32_t)lane < nl) & (jrel < ncols));
+        uint32_t accD = 0, accI = 0, accE = 0, accF = 0;
+        if (active) {
+            const int j = (int)(c0 + jrel);
+            const bool tdash = tc == '-';
+            const int got = tdash ? 0 : OX, get = tdash ? 0 : X;  // horizontal gap step (t[j-1])
+            auto score_of = [&](int r) { return (qbyte(r) == (uint32_t)tc) ? MA : MI; };
+            int dnext = wadd(prev, score_of(0));
+            int upH = recvH, upF = recvF;
+            int stepkey = INT_MIN;
+            static_for<0, R>([&](auto rc) {
+                constexpr int r = decltype(rc)::value;
+                const int old = H[r];
+                const int diag = dnext;
+                if constexpr (r + 1 < R) dnext = wadd(old, score_of(r + 1));
+                const int eo = wadd(old, got), ee = wadd(E[r], get);
+                int ev = max(eo, ee);
+                const int fo = wadd(upH, QDASH ? goq[r] : OX), fe = wadd(upF, QDASH ? geq[r] : X);
+                int f = max(fo, fe);
+                const int m1 = max(diag, ev);
+                int h = (MODE == kLocal) ? max3_imm<0>(m1, f) : max(m1, f);
+                if constexpr (CIGAR) {
+                    const uint64_t mI = ballot(ev > diag);  // INSERT beats MATCH only if strictly greater
+                    const uint64_t mD = ballot(f > m1);     // DELETE only if strictly greater
+                    uint64_t dmask = mD, imask = mI;
+                    if constexpr (MODE == kLocal) {  // canonical codes: M=00 I=01 D=10 STOP=11
+                        const uint64_t mS = ballot(h == 0);  // cost 0 ends the walk (:202)
+                        dmask |= mS;
+                        imask = (mI & ~mD) | mS;
+                    }
+                    accD = shl1_add_lanebit(accD, dmask);
+                    accI = shl1_add_lanebit(accI, imask);
+                    accE = shl1_add_lanebit(accE, ballot(ee > eo));  // extension strictly better
+                    accF = shl1_add_lanebit(accF, ballot(fe > fo));
+                }
+                if constexpr (MASKED) {  // off the band: no cell
+                    const bool inb = (uint32_t)(e - r) <= BW;
+                    h = inb ? h : kSent;
+                    ev = inb ? ev : kSent;
+                    f = inb ? f : kSent;
+                }
+                if constexpr (MODE == kLocal) {  // (kSent << 4 would wrap: an out-of-band cell keys as h = -1)
+                    const int hk = MASKED ? max(h, -1) : h;
+                    stepkey = max(stepkey, (int)(((uint32_t)hk << 4) + (uint32_t)kc[r]));
+                }
+                E[r] = ev;
+                H[r] = h;
+                upH = h;
+                upF = f;
+            });
+            Flast = upF;
+            if constexpr (MODE == kLocal) {
+                if (stepkey > bestkey) {  // strict: the first column keeps a tie (:186)
+                    bestkey = stepkey;
+                    bestj = (uint32_t)j;
+                }
+            }
+            if constexpr (MODE == kSemi) {
+                if (last_pass) {  // row n is register nv-1 of lane nl-1
+                    const int rv = select_row<R>(H, nv - 1);
+                    if (rv > rowbest) {
+                        rowbest = rv;
+                        rowbest_j = (uint32_t)j;
+                    }
+                }
+            }
+            if (has_next && (uint32_t)lane == nl - 1) B[j] = make_int2(H[R - 1], Flast);
+        }
+        if constexpr (CIGAR) prow[t * kWave + lane] = make_uint2((accD << 16) | accI, (accF << 16) | accE);
+        ++e;
+    };
+    // Steps at which every lane in use is at a column of the pass and its whole
+    // stripe is in band: e - 15 >= 0 in lane nl-1 and e <= BW in lane 0.
+    const int e0 = (int)c0 - (int)row_base - 1 - lo;  // lane 0's e at step 0
+    const int t_in = max((int)nl - 1, 15 + 17 * ((int)nl - 1) - e0);
+    const int t_out = min((int)ncols, (int)BW - e0 + 1);  // first masked step after them
+    const uint32_t u0 = (uint32_t)min(max(t_in, 0), (int)steps);
+    const uint32_t u1 = (uint32_t)min(max(t_out, (int)u0), (int)steps);
+    uint32_t t = 0;
+    for (; t < u0; ++t) step(t, std::true_type{});
+    for (; t < u1; ++t) step(t, std::false_type{});
+    for (; t < steps; ++t) step(t, std::true_type{});
+
+    PassOut o{kFloor, 0, 0, kFloor, 0, 0};
+    if constexpr (MODE == kLocal) {
+        // h first over lanes (the row tag only orders rows inside a lane), then the first lane
+        const int hk = (uint32_t)lane < nl ? (bestkey >> 4) : INT_MIN;
+        const int mx = wave_max(hk);
+        const int fl = first_lane(hk == mx);
+        const int key = rdlane(bestkey, fl);
+        o.h = mx;
+        o.i = row_base + (uint32_t)fl * R + (uint32_t)(R - 1 - (key & 15)) + 1;
+        o.j = (uint32_t)rdlane((int)bestj, fl);
+    } else if constexpr (MODE == kSemi) {
+        if (c1 == m) {  // column m (H holds it now), i ascending, strict '>' (:265-270)
+            int cv = kFloor;
+            uint32_t cr = 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if ((uint32_t)r < vlim && H[r] > cv) {
+                    cv = H[r];
+                    cr = r;
+                }
+            const int mx = wave_max(cv);
+            if (mx > kFloor) {
+                const int fl = first_lane(cv == mx && vlim > 0);
+                o.h = mx;
+                o.i = row_base + (uint32_t)fl * R + (uint32_t)rdlane((int)cr, fl) + 1;
+                o.j = m;
+            }
+        }
+        if (last_pass) {
+            o.row_h = rdlane(rowbest, nl - 1);
+            o.row_j = (uint32_t)rdlane((int)rowbest_j, nl - 1);
+        }
+    } else {
+        if (last_pass) o.corner = rdlane(select_row<R>(H, nv - 1), nl - 1);  // H(n, m)
+    }
+    return o;
+}
+
+template <int MODE, bool CIGAR>
+__global__ __launch_bounds__(kBlock) void banded_affine_fill_kernel(BandAffArgs a) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t widx = wave_id();
+    if (widx >= a.count) return;  // wave-uniform
+    const uint32_t p = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.order[a.begin + widx]);
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.qlen[p]);
+    const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.tlen[p]);
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.band[p]);
+    if (n == 0 || m == 0) {  // the affine closed forms: the whole boundary is in band
+        if (lane == 0) {
+            int score = 0;
+            uint32_t gi = 0, gj = 0, tb = 0;
+            if (MODE == kGlobal) {
+                gi = n;
+                gj = m;
+                score = (n || m) ? wadd(a.open, wmul(n ? n : m, a.extend)) : 0;
+            } else if (MODE == kLocal) {
+                tb = 1;
+            } else {
+                gj = (n == 0) ? m : 0;
+            }
+            a.score[p] = score;
+            a.target_begin[p] = tb;
+            a.goal_i[p] = gi;
+            a.goal_j[p] = gj;
+        }
+        return;
+    }
+    const uint8_t* Q = a.qbytes + a.qoff[p];
+    const uint8_t* T = a.tbytes + a.toff[p];
+    const uint32_t passes = n_passes(n);
+    uint2* prow = CIGAR ? a.ptrs + a.ptr_off[p] : nullptr;
+    int2* B = (passes > 1) ? a.bnd + a.bnd_off[p] : nullptr;
+    const int lo = band_lo(n, m, w), hi = band_hi(n, m, w);
+
+    // semi: the column scan starts at (0, m) (cost 0) where that cell is in band
+    int best_h = (MODE == kSemi && (int)m <= hi) ? 0 : kFloor;
+    uint32_t best_i = 0, best_j = (MODE == kSemi) ? m : 0;
+    int corner = 0;
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+        const bool last_pass = pass + 1 == passes;
+        bool dash = false;
+        const uint32_t row0 = pass * kPassRows + (uint32_t)lane * kRows;
+#pragma unroll
+        for (int r = 0; r < kRows; ++r) dash |= (row0 + r < n) && Q[row0 + r] == '-';
+        const PassOut o = __ballot(dash)
+                              ? band_aff_pass<MODE, CIGAR, true>(a, Q, T, n, m, w, pass, last_pass, prow, B, lane)
+                              : band_aff_pass<MODE, CIGAR, false>(a, Q, T, n, m, w, pass, last_pass, prow, B, lane);
+        if (MODE != kGlobal && o.h > best_h) {  // strict: the upper pass wins ties
+            best_h = o.h;
+            best_i = o.i;
+            best_j = o.j;
+        }
+        if (MODE == kSemi && last_pass) {  // row n after column m (:271-278): (n, 0) first, cost 0
+            if (-(int)n >= lo && 0 > best_h) {
+                best_h = 0;
+                best_i = n;
+                best_j = 0;
+            }
+            if (o.row_h > best_h) {
+                best_h = o.row_h;
+                best_i = n;
+                best_j = o.row_j;
+            }
+        }
+        if (MODE == kGlobal && last_pass) corner = o.corner;
+        if (CIGAR) prow += (uint64_t)band_pass_steps(n, m, w, pass) * kWave;
+        if (!last_pass) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // boundary row -> next pass
+    }
+    if (lane == 0) {
+        a.score[p] = (MODE == kGlobal) ? corner : best_h;
+        a.target_begin[p] = (MODE == kLocal) ? best_j + 1 : 0;  // :117-121 / :197-199 / :283-285
+        a.goal_i[p] = (MODE == kGlobal) ? n : best_i;
+        a.goal_j[p] = (MODE == kGlobal) ? m : best_j;
+    }
+}
+
+// The affine three-state walk over the banded entry layout (ta_walk_affine.h
+// AffBandGeo): steps counted from the pass's c0, a pass's first entry from
+// band_pass_offset.  The walk never leaves the band: a candidate from an
+// out-of-band cell never won, so it is in E (F) state only at cells whose left
+// (upper) neighbour is in band, and an M run stays on its diagonal.
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void banded_affine_traceback_kernel(BandAffArgs a) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t widx = wave_id();
+    if (widx >= a.count) return;
+    const uint32_t p = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.order[a.begin + widx]);
+    const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.qlen[p]);
+    const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.tlen[p]);
+    const uint32_t bw = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.band[p]);
+    const uint32_t gi = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.goal_i[p]);
+    const uint32_t gj = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.goal_j[p]);
+    uint64_t st;
+    uint32_t len;
+    aff_traceback_pair<MODE>(a.ptrs + a.ptr_off[p], AffBandGeo{n, m, bw}, n, m, gi, gj, a.slots + a.slot_off[p],
+                             cigar_slot_bytes(n, m), lane, &st, &len);
+    if (lane == 0) {
+        a.cigar_start[p] = a.slot_off[p] + st;
+        a.cigar_len[p] = len;
+    }
+}
+
+inline dim3 band_aff_grid(uint32_t waves) { return dim3((waves + kWavesPerBlock - 1) / kWavesPerBlock); }
+
+hipError_t launch_banded_affine_fill(int mode, bool cigar, const BandAffArgs& a, hipStream_t s) {
+    if (a.count == 0) return hipSuccess;
+    const dim3 g = band_aff_grid(a.count), b(kBlock);
+#define TA_BAND_AFF_FILL(M)                                                                    \
+    case M:                                                                                    \
+        if (cigar) hipLaunchKernelGGL((banded_affine_fill_kernel<M, true>), g, b, 0, s, a);    \
+        else hipLaunchKernelGGL((banded_affine_fill_kernel<M, false>), g, b, 0, s, a);         \
+        break;
+    switch (mode) {
+        TA_BAND_AFF_FILL(kGlobal)
+        TA_BAND_AFF_FILL(kLocal)
+        TA_BAND_AFF_FILL(kSemi)
+        default: return hipErrorInvalidValue;
+    }
+#undef TA_BAND_AFF_FILL
+    return hipGetLastError();
+}
+
+hipError_t launch_banded_affine_traceback(int mode, const BandAffArgs& a, hipStream_t s) {
+    if (a.count == 0) return hipSuccess;
+    const dim3 g = band_aff_grid(a.count), b(kBlock);
+    switch (mode) {
+        case kGlobal: hipLaunchKernelGGL(banded_affine_traceback_kernel<kGlobal>, g, b, 0, s, a); break;
+        case kLocal: hipLaunchKernelGGL(banded_affine_traceback_kernel<kLocal>, g, b, 0, s, a); break;
+        case kSemi: hipLaunchKernelGGL(banded_affine_traceback_kernel<kSemi>, g, b, 0, s, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace
+}  // namespace ta
+
+// ---------------------------------------------------------------------------
+// Host driver (the planning is ta_planner.cpp build_band_affine_plan).
+struct TA_PLAN_LOCAL ta_banded_affine_plan : ta::BandArrays {  // the opaque plan, as the shared driver takes it (ta_plan_driver.h)
+    ta_context* ctx = nullptr;
+    ta::BandAffinePlan h;
+    void* own_block = nullptr;  // device arrays of a plan made by ta_banded_affine_plan_create (one allocation)
+    static int exec_chunk(ta_banded_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill,
+                          bool trace);
+    uint32_t* err_word() const { return nullptr; }  // (no polls: one wave sweeps a pair's passes)
+    static const char* err_message(uint32_t) { return ""; }
+};
+
+namespace {
+
+using ta_host::fail;
+
+int band_aff_check_args(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
+                        const uint32_t* band, int type, int match, int mismatch, int gap_open, int gap_extend) {
+    if (!ctx) return TA_ERR_ARG;
+    if (n_pairs && (!qlen || !tlen || !band)) return fail(ctx, TA_ERR_ARG, "null argument");
+    if (!ta_host::valid_type(type)) return fail(ctx, TA_ERR_BAD_TYPE, ta_status_string(TA_ERR_BAD_TYPE));
+    const long long max_step = std::max({std::llabs(match), std::llabs(mismatch),
+                                         std::llabs(gap_open) + std::llabs(gap_extend)});
+    if (!ta_host::in_range(n_pairs, qlen, tlen, max_step))
+        return fail(ctx, TA_ERR_RANGE, ta_status_string(TA_ERR_RANGE));
+    return TA_OK;
+}
+
+}  // namespace
+
+int ta_banded_affine_plan::exec_chunk(ta_banded_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c,
+                                      bool fill, bool trace) {
+    ta_context* ctx = pl->ctx;
+    const ta::BandAffinePlan& h = pl->h;
+    if (int r = ta_host::grow(ctx, ctx->ws_ptrs, h.ws_ptr_entries * sizeof(uint2))) return r;
+    if (int r = ta_host::grow(ctx, ctx->ws_bnd, h.ws_bnd_entries * sizeof(int2))) return r;
+    const auto& ch = h.chunks[c];
+    ta::BandAffArgs a{};
+    a.order = pl->d_order;
+    a.begin = ch.begin;
+    a.count = ch.count;
+    a.qbytes = (const uint8_t*)io->query_bytes;
+    a.qoff = io->query_off;
+    a.qlen = pl->d_qlen;
+    a.tbytes = (const uint8_t*)io->target_bytes;
+    a.toff = io->target_off;
+    a.tlen = pl->d_tlen;
+    a.band = pl->d_band;
+    a.match = h.match;
+    a.mismatch = h.mismatch;
+    a.open = h.open;
+    a.extend = h.extend;
+    a.ptrs = (uint2*)ctx->ws_ptrs.p;
+    a.ptr_off = pl->d_ptr_off;
+    a.bnd = (int2*)ctx->ws_bnd.p;
+    a.bnd_off = pl->d_bnd_off;
+    a.score = io->score;
+    a.target_begin = io->target_begin;
+    a.goal_i = pl->d_goal_i;
+    a.goal_j = pl->d_goal_j;
+    a.slots = io->cigar_slots;
+    a.slot_off = pl->d_slot_off;
+    a.cigar_start = io->cigar_start;
+    a.cigar_len = io->cigar_len;
+    if (fill) {
+        roctxRangePushA("ta banded affine fill");
+        TA_HIP(ctx, ta::launch_banded_affine_fill(h.type, h.want_cigar, a, s));
+        roctxRangePop();
+    }
+    if (trace && h.want_cigar) {
+        roctxRangePushA("ta banded affine traceback");
+        TA_HIP(ctx, ta::launch_banded_affine_traceback(h.type, a, s));
+        roctxRangePop();
+    }
+    return TA_OK;
+}
+
+extern "C" {
+
+void ta_banded_affine_plan_destroy(ta_banded_affine_plan* pl) { ta_host::plan_destroy(pl); }
+
+int ta_banded_affine_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
+                                 const uint32_t* band, int type, int match, int mismatch, int gap_open, int gap_extend,
+                                 int want_cigar, uint64_t budget, uint32_t flags, ta_banded_affine_plan** out) {
+    if (!out) return TA_ERR_ARG;
+    *out = nullptr;
+    if (int r = band_aff_check_args(ctx, n_pairs, qlen, tlen, band, type, match, mismatch, gap_open, gap_extend))
+        return r;
+    if (flags) return fail(ctx, TA_ERR_ARG, "ta_banded_affine_plan_create: flags must be 0");
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    auto* pl = new ta_banded_affine_plan();
+    pl->ctx = ctx;
+    ta::build_band_affine_plan(pl->h, n_pairs, qlen, tlen, band, type, match, mismatch, gap_open, gap_extend,
+                               want_cigar != 0, budget ? budget : ta_host::default_budget(ctx));
+    return ta_host::plan_create_block(pl, "ta_banded_affine_plan_create: ", out);
+}
+
+uint64_t ta_banded_affine_plan_cigar_slots_bytes(const ta_banded_affine_plan* pl) { return pl ? pl->h.slots_bytes : 0; }
+uint64_t ta_banded_affine_plan_workspace_bytes(const ta_banded_affine_plan* pl) {
+    return pl ? pl->h.ws_ptr_entries * sizeof(uint2) + pl->h.ws_bnd_entries * sizeof(int2) : 0;
+}
+uint32_t ta_banded_affine_plan_chunks(const ta_banded_affine_plan* pl) { return pl ? (uint32_t)pl->h.chunks.size() : 0; }
+uint64_t ta_banded_affine_plan_band_cells(const ta_banded_affine_plan* pl) { return pl ? pl->h.band_cells : 0; }
+uint64_t ta_banded_affine_plan_swept_cells(const ta_banded_affine_plan* pl) { return pl ? pl->h.swept_cells : 0; }
+
+int ta_banded_affine_plan_pair_chunks(const ta_banded_affine_plan* pl, uint32_t* chunk_of_pair) {
+    return ta_host::plan_pair_chunks(pl, chunk_of_pair);
+}
+int ta_banded_affine_plan_check(ta_banded_affine_plan* pl) { return ta_host::plan_check(pl); }
+int ta_banded_affine_plan_execute(ta_banded_affine_plan* pl, const ta_device_io* io, void* stream) {
+    return ta_host::plan_execute(pl, io, stream);
+}
+int ta_banded_affine_plan_execute_fill(ta_banded_affine_plan* pl, const ta_device_io* io, void* stream,
+                                       uint32_t chunk) {
+    return ta_host::plan_execute_chunk(pl, io, stream, chunk, true);
+}
+int ta_banded_affine_plan_execute_traceback(ta_banded_affine_plan* pl, const ta_device_io* io, void* stream,
+                                            uint32_t chunk) {
+    return ta_host::plan_execute_chunk(pl, io, stream, chunk, false);
+}
+int ta_banded_affine_plan_annotate(ta_banded_affine_plan* pl, const ta_device_io* io, const ta_annotate_io* out,
+                                   void* stream) {
+    return ta_host::plan_annotate(pl, io, out, stream);
+}
+
+int ta_align_batch_banded_affine(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
+                                 const uint32_t* qlen, const char* tbytes, const uint64_t* toff, const uint32_t* tlen,
+                                 const uint32_t* band, int type, int match, int mismatch, int gap_open,
+                                 int gap_extend, int want_cigar, int32_t* score, uint32_t* target_begin, char* arena,
+                                 uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len) {
+    uint64_t qend = 0, tend = 0;
+    if (int r = ta_host::check_host_batch(ctx, type, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, want_cigar, arena,
+                                          cigar_off, cigar_len, &qend, &tend))
+        return r;
+    if (n_pairs == 0) return TA_OK;
+    if (int r = band_aff_check_args(ctx, n_pairs, qlen, tlen, band, type, match, mismatch, gap_open, gap_extend))
+        return r;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    ta_banded_affine_plan pl;
+    pl.ctx = ctx;
+    uint64_t need = 0;
+    if (want_cigar)
+        for (uint32_t p = 0; p < n_pairs; ++p) need += sizeof(uint2) * ta::band_ptr_dwords(qlen[p], tlen[p], band[p]);
+    // everything in one chunk while the codes take at most 1 GiB (no device query per call)
+    const uint64_t budget = need <= (1ull << 30) ? std::max<uint64_t>(need, 1) : ta_host::default_budget(ctx);
+    ta::build_band_affine_plan(pl.h, n_pairs, qlen, tlen, band, type, match, mismatch, gap_open, gap_extend,
+                               want_cigar != 0, budget);
+    return ta_host::host_batch(ctx, pl, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
+                               target_begin, arena, arena_bytes, cigar_off, cigar_len);
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // bioinfo1_amd/csrc/ta_host_batch.h -- the host-memory batch driver shared by
-// ta_align_batch (linear gap), ta_align_batch_affine and ta_align_batch_banded:
+// ta_align_batch (linear gap), ta_align_batch_affine, ta_align_batch_banded and ta_align_batch_banded_affine:
 // host arrays in, host arrays out, no device allocation or free per call once the context's
 // grow-only buffers are large enough.
 //

@@ -115,15 +115,16 @@ void block_arrays(const AffinePlan& h, AffineArrays& d, V& v) {
     v.scratch(d.d_spout, h.single_tasks.size() * 24ull);
 }
 
-// ---- banded (ta_banded.hip)
+// ---- banded (ta_banded.hip) and banded affine (ta_banded_affine.hip): the
+// same arrays; the families differ in the size of a code and boundary entry
 struct BandArrays {
     uint32_t *d_qlen = nullptr, *d_tlen = nullptr, *d_band = nullptr, *d_order = nullptr;
     uint32_t *d_goal_i = nullptr, *d_goal_j = nullptr;
     uint64_t *d_ptr_off = nullptr, *d_bnd_off = nullptr, *d_slot_off = nullptr;
 };
 
-template <class V>
-void block_arrays(const BandPlan& h, BandArrays& d, V& v) {
+template <class H, class V>
+void band_block_arrays(const H& h, BandArrays& d, V& v) {
     v.vec(d.d_qlen, h.qlen);
     v.vec(d.d_tlen, h.tlen);
     v.vec(d.d_band, h.band);
@@ -134,6 +135,14 @@ void block_arrays(const BandPlan& h, BandArrays& d, V& v) {
     v.device_only();
     v.scratch(d.d_goal_i, 4ull * h.n_pairs);
     v.scratch(d.d_goal_j, 4ull * h.n_pairs);
+}
+template <class V>
+void block_arrays(const BandPlan& h, BandArrays& d, V& v) {
+    band_block_arrays(h, d, v);
+}
+template <class V>
+void block_arrays(const BandAffinePlan& h, BandArrays& d, V& v) {
+    band_block_arrays(h, d, v);
 }
 
 // ---- the three visitors

@@ -1,6 +1,6 @@
-// bioinfo1_amd/csrc/ta_plan_driver.h -- what the host drivers of the three
-// plan families share (linear gap: ta_api.hip, affine gap: ta_affine.hip,
-// banded: ta_banded.hip): device-resident create / destroy, the argument
+// bioinfo1_amd/csrc/ta_plan_driver.h -- what the host drivers of the plan
+// families share (linear gap: ta_api.hip, affine gap: ta_affine.hip, banded:
+// ta_banded.hip, banded affine: ta_banded_affine.hip): device-resident create / destroy, the argument
 // checks of an execution, the chunk loop, pair_chunks, annotate and the error
 // word's check.  The extern "C" entries of include/team_align_c.h forward here.
 //

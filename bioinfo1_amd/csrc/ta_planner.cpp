@@ -639,12 +639,14 @@ void build_affine_plan(AffinePlan& pl, uint32_t n_pairs, const uint32_t* qlen, c
 }
 
 // The degenerate case of the assembly: single pairs by descending swept cells,
-// no wave quantum, no hand-off records.
-void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
-                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget) {
-    pl = BandPlan{};
-    init_plan(pl, n_pairs, qlen, tlen, type, match, mismatch, want_cigar);
-    pl.gap = gap;
+// no wave quantum, no hand-off records.  Both banded families: the entry
+// counts are the same (band_ptr_dwords code entries, bnd_words boundary
+// entries); the families differ in the size of an entry.
+namespace {
+
+template <class P>
+Assembly assemble_band(P& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
+                       uint64_t budget_entries) {
     pl.band.resize(n_pairs);
     std::vector<Unit> units(n_pairs);
     for (uint32_t p = 0; p < n_pairs; ++p) {
@@ -654,13 +656,36 @@ void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const
         pl.band_cells += band_cells(qlen[p], tlen[p], pl.band[p]);
     }
     std::stable_sort(units.begin(), units.end(), [](const Unit& x, const Unit& y) { return x.cost > y.cost; });
-    const Assembly as = assemble_chunks(
-        pl, units, std::max<uint64_t>(budget / 4, 1), 0, false,
+    return assemble_chunks(
+        pl, units, std::max<uint64_t>(budget_entries, 1), 0, false,
         [&](uint32_t p) { return band_ptr_dwords(qlen[p], tlen[p], pl.band[p]); },
         [&](const Unit& u, int) { return bnd_words(qlen[u.a], tlen[u.a]); });
+}
+
+}  // namespace
+
+void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
+                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget) {
+    pl = BandPlan{};
+    init_plan(pl, n_pairs, qlen, tlen, type, match, mismatch, want_cigar);
+    pl.gap = gap;
+    const Assembly as = assemble_band(pl, n_pairs, qlen, tlen, band, budget / 4);
     for (const Cut& c : as.cuts) pl.chunks.push_back({{c.begin, c.count}, c.codes, c.bnd});
     pl.ws_ptr_dwords = as.ws_codes;
     pl.ws_bnd_words = as.ws_bnd;
+}
+
+void build_band_affine_plan(BandAffinePlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
+                            const uint32_t* band, int type, int match, int mismatch, int gap_open, int gap_extend,
+                            bool want_cigar, uint64_t budget) {
+    pl = BandAffinePlan{};
+    init_plan(pl, n_pairs, qlen, tlen, type, match, mismatch, want_cigar);
+    pl.open = gap_open;
+    pl.extend = gap_extend;
+    const Assembly as = assemble_band(pl, n_pairs, qlen, tlen, band, budget / 8);
+    for (const Cut& c : as.cuts) pl.chunks.push_back({{c.begin, c.count}, c.codes, c.bnd});
+    pl.ws_ptr_entries = as.ws_codes;
+    pl.ws_bnd_entries = as.ws_bnd;
 }
 
 uint64_t host_batch_code_bytes(uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, uint64_t bytes_per_entry) {

@@ -1,8 +1,9 @@
 // bioinfo1_amd/csrc/ta_planner.h -- host planning of a batch (no HIP):
 // which kernel each pair runs in, the visit order, the chunks the 2-bit
 // traceback-code workspace is cut into, and every per-pair offset the kernels
-// read, for the three plan families: linear gap, affine gap and banded.  The
-// device side (ta_api.hip / ta_affine.hip / ta_banded.hip, through
+// read, for the plan families: linear gap, affine gap, banded and banded
+// affine.  The device side (ta_api.hip / ta_affine.hip / ta_banded.hip /
+// ta_banded_affine.hip, through
 // ta_plan_driver.h) uploads the arrays packed into one block (ta_plan_block.h)
 // and launches per chunk.  Pure C++ so that it builds with g++ for the CPU
 // tests and the ASan/UBSan/TSan runs (tests/test_host_sanitizers.py).
@@ -40,7 +41,7 @@ bool flex_ck_fits(int mode, uint32_t n, uint32_t m, int match, int mismatch, int
 // Every packed value of the affine dual fill (ta_affine.hip) within int16.
 bool affine_fits_int16(int mode, uint32_t n, uint32_t m, int ma, int mi, int open, int ext);
 
-// What the three plan families share, in name and meaning: the batch, the
+// What the plan families share, in name and meaning: the batch, the
 // visit order, and per pair the offsets of its codes and boundary row inside
 // its chunk (in the family's entries) and of its CIGAR slot (bytes).
 struct PlanBase {
@@ -154,6 +155,25 @@ struct BandPlan : PlanBase {
 // budget = bytes of 2-bit codes per chunk (> 0); band[p] is clamped to its pair (ta_layout.h band_clamp).
 void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
                      int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget);
+
+// Banded affine plan (the banded affine extension of include/team_align_c.h):
+// the banded plan with 8-byte code entries (one uint2 per (pass, swept step,
+// lane), counted by band_ptr_dwords) and int2 (H, F) boundary entries.
+struct BandAffinePlan : PlanBase {
+    int open = 0, extend = 0;
+    std::vector<uint32_t> band;  // per pair, clamped
+    struct Chunk : ChunkSpan {
+        uint64_t ptr_entries, bnd_entries;
+    };
+    std::vector<Chunk> chunks;
+    uint64_t ws_ptr_entries = 0, ws_bnd_entries = 0;
+    uint64_t band_cells = 0, swept_cells = 0;
+};
+
+// budget = bytes of 4-bit codes (8-byte entries) per chunk (> 0); order and chunking as build_band_plan.
+void build_band_affine_plan(BandAffinePlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
+                            const uint32_t* band, int type, int match, int mismatch, int gap_open, int gap_extend,
+                            bool want_cigar, uint64_t budget);
 
 // One contiguous block holding several arrays, each at a 256-byte aligned
 // offset: the plan's per-pair arrays go to the device in one copy.

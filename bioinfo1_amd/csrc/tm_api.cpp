@@ -229,12 +229,13 @@ int tm_map_batch(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const c
                           score, arena, arena_bytes, cigar_off, cigar_len, 0, nullptr);
 }
 
-// band: null = no band, the reference-exact ta_plan_*; else every window's band (ta_banded_plan_*)
+// band: null = no band, the reference-exact ta_plan_*; else every window's band (ta_banded_plan_*).
+// gap_open (with a band only): affine gaps, gap_extend = opt->gap (ta_banded_affine_plan_*).
 static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
                           const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
                           uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end,
                           int32_t* score, char* arena, uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
-                          uint32_t flags, ta_pair_info* info, const uint32_t* band);
+                          uint32_t flags, ta_pair_info* info, const uint32_t* band, const int* gap_open = nullptr);
 
 int tm_map_batch_x(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes, const uint64_t* off,
                    const uint32_t* len, const tm_options* opt, uint8_t* mapped, uint8_t* strand_fwd, uint32_t* q_begin,
@@ -253,11 +254,20 @@ int tm_map_batch_band(tm_context* ctx, const tm_index* idx, uint32_t n_reads, co
                           score, arena, arena_bytes, cigar_off, cigar_len, flags, info, &band);
 }
 
+int tm_map_batch_band_affine(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
+                             const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
+                             uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin,
+                             uint32_t* t_end, int32_t* score, char* arena, uint64_t arena_bytes, uint64_t* cigar_off,
+                             uint32_t* cigar_len, uint32_t flags, ta_pair_info* info, uint32_t band, int gap_open) {
+    return map_batch_impl(ctx, idx, n_reads, bytes, off, len, opt, mapped, strand_fwd, q_begin, q_end, t_begin, t_end,
+                          score, arena, arena_bytes, cigar_off, cigar_len, flags, info, &band, &gap_open);
+}
+
 static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
                           const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
                           uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end,
                           int32_t* score, char* arena, uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
-                          uint32_t flags, ta_pair_info* info, const uint32_t* band) {
+                          uint32_t flags, ta_pair_info* info, const uint32_t* band, const int* gap_open) {
     if (!ctx || !idx || !opt) return TM_ERR_ARG;
     if (flags & ~TM_MAP_EQX) return fail(ctx, TM_ERR_ARG, "unknown flag");
     if (info && !(flags & TM_MAP_EQX)) return fail(ctx, TM_ERR_ARG, "info needs TM_MAP_EQX");
@@ -345,6 +355,7 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
     if (!P) return TM_OK;
     ta_plan* plan = nullptr;
     ta_banded_plan* bplan = nullptr;  // with a band: the banded family instead (the same band for every window)
+    ta_banded_affine_plan* aplan = nullptr;  // with a band and a gap open: the banded affine family
     // the mapper owns the device: its code workspace may take most of the free
     // HBM (fewer, fuller chunks for long reads; the library default is half,
     // <= 64 GiB).  Memory the alignment context already holds from the last
@@ -354,7 +365,12 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
                                 ? ((uint64_t)free_b + ta_context_held_bytes(ctx->ta)) / 100 * 85
                                 : 0;
     int rc;
-    if (band) {
+    if (band && gap_open) {
+        const std::vector<uint32_t> bw(P, *band);
+        rc = ta_banded_affine_plan_create(ctx->ta, P, ql.data(), tl.data(), bw.data(), opt->type, opt->match,
+                                          opt->mismatch, *gap_open, opt->gap, opt->want_cigar || eqx, budget, 0,
+                                          &aplan);
+    } else if (band) {
         const std::vector<uint32_t> bw(P, *band);
         rc = ta_banded_plan_create(ctx->ta, P, ql.data(), tl.data(), bw.data(), opt->type, opt->match, opt->mismatch,
                                    opt->gap, opt->want_cigar || eqx, budget, 0, &bplan);
@@ -364,7 +380,9 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
     }
     if (rc != TA_OK) return fail(ctx, rc == TA_ERR_BAD_TYPE ? TM_ERR_BAD_TYPE : TM_ERR_DEVICE,
                                  std::string("ta_plan_create: ") + ta_last_error(ctx->ta));
-    const uint64_t slots = band ? ta_banded_plan_cigar_slots_bytes(bplan) : ta_plan_cigar_slots_bytes(plan);
+    const uint64_t slots = aplan   ? ta_banded_affine_plan_cigar_slots_bytes(aplan)
+                           : bplan ? ta_banded_plan_cigar_slots_bytes(bplan)
+                                   : ta_plan_cigar_slots_bytes(plan);
     auto run = [&]() -> int {
         TM_HIP(ctx, ctx->m_qoff.reserve(P * 8ull));
         TM_HIP(ctx, ctx->m_toff.reserve(P * 8ull));
@@ -386,7 +404,9 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
         io.cigar_start = ctx->m_cstart.as<uint64_t>();
         io.cigar_len = ctx->m_clen.as<uint32_t>();
         if (int r = stage(4)) return r;
-        if (int r = band ? ta_banded_plan_execute(bplan, &io, s) : ta_plan_execute(plan, &io, s))
+        if (int r = aplan   ? ta_banded_affine_plan_execute(aplan, &io, s)
+                    : bplan ? ta_banded_plan_execute(bplan, &io, s)
+                            : ta_plan_execute(plan, &io, s))
             return fail(ctx, TM_ERR_DEVICE, std::string("ta_plan_execute: ") + ta_last_error(ctx->ta) + " (" +
                                                 ta_status_string(r) + ")");
         if (int r = stage(5)) return r;
@@ -409,7 +429,9 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
                 c_start = ao.eqx_start;
                 c_len = ao.eqx_len;
             }
-            if (int r = band ? ta_banded_plan_annotate(bplan, &io, &ao, s) : ta_plan_annotate(plan, &io, &ao, s))
+            if (int r = aplan   ? ta_banded_affine_plan_annotate(aplan, &io, &ao, s)
+                        : bplan ? ta_banded_plan_annotate(bplan, &io, &ao, s)
+                                : ta_plan_annotate(plan, &io, &ao, s))
                 return fail(ctx, TM_ERR_DEVICE, std::string("ta_plan_annotate: ") + ta_last_error(ctx->ta) + " (" +
                                                     ta_status_string(r) + ")");
             if (info) {
@@ -432,7 +454,7 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
             if (total) TM_HIP(ctx, hipMemcpyAsync(arena, ctx->m_cdst.p, total, hipMemcpyDeviceToHost, s));
         }
         TM_HIP(ctx, hipStreamSynchronize(s));
-        if (int r = band ? ta_banded_plan_check(bplan) : ta_plan_check(plan))
+        if (int r = aplan ? ta_banded_affine_plan_check(aplan) : bplan ? ta_banded_plan_check(bplan) : ta_plan_check(plan))
             return fail(ctx, TM_ERR_DEVICE, std::string("ta_plan_check: ") + ta_last_error(ctx->ta) + " (" +
                                                 ta_status_string(r) + ")");
         for (uint32_t p = 0; p < P; ++p) {
@@ -446,13 +468,16 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
         return TM_OK;
     };
     ctx->plan_stats[0] = P;
-    ctx->plan_stats[1] = band ? ta_banded_plan_chunks(bplan) : ta_plan_chunks(plan);
+    ctx->plan_stats[1] = aplan ? ta_banded_affine_plan_chunks(aplan) : bplan ? ta_banded_plan_chunks(bplan) : ta_plan_chunks(plan);
     ctx->plan_stats[2] = band ? 0 : ta_plan_dual_pairs(plan);
     ctx->plan_stats[3] = band ? 0 : ta_plan_flex_pairs(plan);
-    ctx->plan_stats[4] = band ? ta_banded_plan_workspace_bytes(bplan) : ta_plan_workspace_bytes(plan);
+    ctx->plan_stats[4] = aplan   ? ta_banded_affine_plan_workspace_bytes(aplan)
+                         : bplan ? ta_banded_plan_workspace_bytes(bplan)
+                                 : ta_plan_workspace_bytes(plan);
     rc = run();
     ta_plan_destroy(plan);
     ta_banded_plan_destroy(bplan);
+    ta_banded_affine_plan_destroy(aplan);
     if (rc == TM_OK) rc = stage(6);
     ctx->stage_cells = 0;
     for (uint32_t p = 0; p < P; ++p) ctx->stage_cells += (uint64_t)ql[p] * tl[p];
@@ -478,7 +503,8 @@ int tm_map_files(const char* reference_path, const char* reads_path, const tm_op
 }
 
 static int map_files_impl(const char* reference_path, const char* reads_path, const tm_options* opt,
-                          const char* out_path, int device, uint32_t flags, const uint32_t* band);
+                          const char* out_path, int device, uint32_t flags, const uint32_t* band,
+                          const int* gap_open = nullptr);
 
 int tm_map_files_x(const char* reference_path, const char* reads_path, const tm_options* opt, const char* out_path,
                    int device, uint32_t flags) {
@@ -490,8 +516,13 @@ int tm_map_files_band(const char* reference_path, const char* reads_path, const 
     return map_files_impl(reference_path, reads_path, opt, out_path, device, flags, &band);
 }
 
+int tm_map_files_band_affine(const char* reference_path, const char* reads_path, const tm_options* opt,
+                             const char* out_path, int device, uint32_t flags, uint32_t band, int gap_open) {
+    return map_files_impl(reference_path, reads_path, opt, out_path, device, flags, &band, &gap_open);
+}
+
 static int map_files_impl(const char* reference_path, const char* reads_path, const tm_options* opt,
-                          const char* out_path, int device, uint32_t flags, const uint32_t* band) {
+                          const char* out_path, int device, uint32_t flags, const uint32_t* band, const int* gap_open) {
     if (!reference_path || !reads_path || !opt || !out_path || (flags & ~TM_MAP_EQX)) return TM_ERR_ARG;
     const bool eqx = (flags & TM_MAP_EQX) != 0;
     tmap::FastxFile ref, reads;
@@ -549,7 +580,7 @@ static int map_files_impl(const char* reference_path, const char* reads_path, co
         std::vector<ta_pair_info> info(eqx ? nr : 0);
         rc = map_batch_impl(ctx, idx, nr, reads.seq.data() + base, off.data(), len.data(), &o, mapped.data(),
                             fwd.data(), qb.data(), qe.data(), tb.data(), te.data(), sc.data(), arena.data(), arena.size(),
-                            co.data(), cl.data(), flags, eqx ? info.data() : nullptr, band);
+                            co.data(), cl.data(), flags, eqx ? info.data() : nullptr, band, gap_open);
         if (rc) {
             std::fprintf(stderr, "map: %s: %s\n", tm_status_string(rc), tm_last_error(ctx));
             break;

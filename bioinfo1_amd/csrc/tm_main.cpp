@@ -1,6 +1,8 @@
 // bioinfo1_amd/csrc/tm_main.cpp -- team_mapper_amd: the reference mapper's
 // command line (team_mapper.cpp:165-180, 319-396) over the MI355X pipeline
 // (tm_map_files).  PAF-like lines go to stdout in read order.
+#include <cerrno>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,6 +41,8 @@ int main(int argc, char** argv) {
     unsigned flags = 0;  // --eqx: =/X CIGARs and an NM tag (not in help(), which restates the reference's text)
     bool banded = false;  // --band N: every window through the banded extension (not in help() either)
     unsigned band = 0;
+    bool affine = false;  // --gap-open O (with --band): affine gaps, -g is the gap extend (not in help() either)
+    int gap_open = 0;
     if (argc < 2) {
         std::fprintf(stderr, "Error: Not enough arguments\n");
         help();
@@ -88,6 +92,17 @@ int main(int argc, char** argv) {
             banded = true;
             band = (unsigned)v;
         }
+        else if (!std::strcmp(a, "--gap-open") && more) {
+            char* end = nullptr;
+            errno = 0;
+            const long v = std::strtol(argv[++i], &end, 10);
+            if (end == argv[i] || *end || errno || v < INT_MIN || v > INT_MAX) {
+                std::fprintf(stderr, "Error: --gap-open expects a decimal integer\n");
+                return 1;
+            }
+            affine = true;
+            gap_open = (int)v;
+        }
         else if (!std::strcmp(a, "-s")) std::fprintf(stderr, "note: -s (statistics) is not part of this build\n");
         else if (f1.empty()) f1 = a;
         else if (f2.empty()) f2 = a;
@@ -102,8 +117,13 @@ int main(int argc, char** argv) {
         help();
         return 1;
     }
-    const int r = banded ? tm_map_files_band(f1.c_str(), f2.c_str(), &o, "-", device, flags, band)
-                         : tm_map_files_x(f1.c_str(), f2.c_str(), &o, "-", device, flags);
+    if (affine && !banded) {
+        std::fprintf(stderr, "Error: --gap-open requires --band (there is no unbanded affine mapper path)\n");
+        return 1;
+    }
+    const int r = affine   ? tm_map_files_band_affine(f1.c_str(), f2.c_str(), &o, "-", device, flags, band, gap_open)
+                  : banded ? tm_map_files_band(f1.c_str(), f2.c_str(), &o, "-", device, flags, band)
+                           : tm_map_files_x(f1.c_str(), f2.c_str(), &o, "-", device, flags);
     if (r != TM_OK && r != TM_ERR_INPUT) std::fprintf(stderr, "error: %s\n", tm_status_string(r));
     return r == TM_OK ? 0 : 1;
 }

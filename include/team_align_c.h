@@ -492,6 +492,81 @@ int ta_align_batch_banded(ta_context* ctx, uint32_t n_pairs, const char* query_b
                           int gap, int want_cigar, int32_t* score, uint32_t* target_begin, char* cigar_arena,
                           uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len);
 
+/*
+ * ---- Banded affine extension: the affine-gap extension inside the banded
+ * extension's band.  Work and code workspace grow with n * band (4 bits of
+ * traceback code per swept cell) instead of n * m.  Neither the reference nor
+ * the two extensions above have a counterpart; it is a plan family of its own
+ * and nothing above changes behaviour.
+ *
+ * Definition, for a pair of lengths n (query) and m (target) and its band w:
+ *   The band is the banded extension's: cell (i, j), 0 <= i <= n, 0 <= j <= m,
+ *   exists iff lo <= j - i <= hi, lo = min(0, m - n) - w, hi = max(0, m - n) + w;
+ *   boundary cells (row 0, column 0) obey the same rule.
+ *   The recurrence is oracle/affine_oracle.c's Gotoh H/E/F with the cells
+ *   outside the band not existing (go_t = gap_open + gap_extend and
+ *   ge_t = gap_extend, both 0 at a '-' byte of the sequence the step consumes):
+ *     E(i, j) = max(H(i, j-1) + go_t, E(i, j-1) + ge_t) when (i, j-1) is in
+ *       band, else -inf; its extension bit is "2nd > 1st", strict.
+ *     F(i, j) the same over (i-1, j).
+ *     MATCH (the diagonal, whose predecessor lies on the same diagonal) is
+ *     always a candidate of an in-band interior cell; INSERT wins iff
+ *     E > diag, DELETE iff F > max(diag, E), both strict.  The local clamp
+ *     keeps the source.
+ *   Boundaries: H(i, 0) and H(0, j) are gap_open + L * gap_extend (global; 0
+ *   at (0, 0)) or 0, where in band; E(i, 0) = F(0, j) = -inf.
+ *   Goals are the banded extension's.  Global: (n, m).  Local: the first
+ *   strict row-major maximum over the in-band interior cells, target_begin =
+ *   gj + 1.  Semi-global: column m with i ascending, then row n, strict '>',
+ *   over in-band cells only.
+ *   The three-state walk, the reversal, the semi-global trailing run, the RLE
+ *   and "1\0" are the affine oracle's.
+ *   Degenerate pairs (n == 0 or m == 0): the affine closed forms (global:
+ *   gap_open + L * gap_extend for L > 0, 0 for the empty pair).
+ * With gap_open == 0 the results equal the banded extension's with gap =
+ * gap_extend, at every band; with w >= max(n, m) they equal the affine
+ * extension's; with every cell the unbanded affine walk visits in band they
+ * equal the unbanded affine ones; a banded score is never above the unbanded
+ * affine score.
+ * Range: (max qlen + max tlen + 2) * max(|match|, |mismatch|,
+ * |gap_open| + |gap_extend|) must be < 2^26, else TA_ERR_RANGE.
+ */
+typedef struct ta_banded_affine_plan ta_banded_affine_plan;
+
+/* As ta_banded_plan_create, with gap -> (gap_open, gap_extend).  Codes take
+ * 8 bytes per (pass, swept step, lane).  flags must be 0 (TA_ERR_ARG). */
+int ta_banded_affine_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* query_len_host,
+                                 const uint32_t* target_len_host, const uint32_t* band_host, int type, int match,
+                                 int mismatch, int gap_open, int gap_extend, int want_cigar,
+                                 uint64_t workspace_budget, uint32_t flags, ta_banded_affine_plan** out);
+void ta_banded_affine_plan_destroy(ta_banded_affine_plan* plan);
+uint64_t ta_banded_affine_plan_cigar_slots_bytes(const ta_banded_affine_plan* plan);
+uint64_t ta_banded_affine_plan_workspace_bytes(const ta_banded_affine_plan* plan);
+uint32_t ta_banded_affine_plan_chunks(const ta_banded_affine_plan* plan);
+int ta_banded_affine_plan_pair_chunks(const ta_banded_affine_plan* plan, uint32_t* chunk_of_pair);
+/* As ta_banded_plan_band_cells / _swept_cells. */
+uint64_t ta_banded_affine_plan_band_cells(const ta_banded_affine_plan* plan);
+uint64_t ta_banded_affine_plan_swept_cells(const ta_banded_affine_plan* plan);
+/* Enqueue the whole batch / one chunk's fill / one chunk's traceback on hip_stream. */
+int ta_banded_affine_plan_execute(ta_banded_affine_plan* plan, const ta_device_io* io, void* hip_stream);
+int ta_banded_affine_plan_execute_fill(ta_banded_affine_plan* plan, const ta_device_io* io, void* hip_stream,
+                                       uint32_t chunk);
+int ta_banded_affine_plan_execute_traceback(ta_banded_affine_plan* plan, const ta_device_io* io, void* hip_stream,
+                                            uint32_t chunk);
+/* As ta_plan_check (these kernels have no failure to report: TA_OK). */
+int ta_banded_affine_plan_check(ta_banded_affine_plan* plan);
+/* As ta_plan_annotate, for a banded affine plan's execution. */
+int ta_banded_affine_plan_annotate(ta_banded_affine_plan* plan, const ta_device_io* io, const ta_annotate_io* out,
+                                   void* hip_stream);
+
+/* Host-memory batch: ta_align_batch_banded with gap -> (gap_open, gap_extend). */
+int ta_align_batch_banded_affine(ta_context* ctx, uint32_t n_pairs, const char* query_bytes,
+                                 const uint64_t* query_off, const uint32_t* query_len, const char* target_bytes,
+                                 const uint64_t* target_off, const uint32_t* target_len, const uint32_t* band,
+                                 int type, int match, int mismatch, int gap_open, int gap_extend, int want_cigar,
+                                 int32_t* score, uint32_t* target_begin, char* cigar_arena,
+                                 uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len);
+
 #ifdef __cplusplus
 }
 #endif

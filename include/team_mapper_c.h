@@ -142,6 +142,18 @@ int tm_map_batch_band(tm_context* ctx, const tm_index* idx, uint32_t n_reads, co
                       char* cigar_arena, uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
                       uint32_t flags, ta_pair_info* info, uint32_t band);
 
+/* tm_map_batch_band with affine gaps: every window is aligned by the banded
+ * affine extension (ta_banded_affine_plan_*, team_align_c.h) with this band,
+ * gap_open and gap_extend = opt->gap.  gap_open == 0 gives tm_map_batch_band's
+ * results.  The mapper has no unbanded affine path; a band of 4294967295 holds
+ * every window's whole matrix. */
+int tm_map_batch_band_affine(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
+                             const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
+                             uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin,
+                             uint32_t* t_end, int32_t* score, char* cigar_arena, uint64_t cigar_arena_bytes,
+                             uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags, ta_pair_info* info,
+                             uint32_t band, int gap_open);
+
 /* Wall time (ms) of the last tm_map_batch on this context, per stage:
  * [0] read upload, [1] minimizers, [2] seed matching, [3] FindLIS chaining,
  * [4] windows + alignment plan (host), [5] alignment (fill + traceback),
@@ -152,7 +164,7 @@ int tm_stage_times(const tm_context* ctx, double* ms, uint32_t n, uint64_t* alig
 /* The alignment plan of the last tm_map_batch: out[0] pairs, [1] chunks,
  * [2] pairs on the packed int16 fills (dual + flexible), [3] pairs on the
  * flexible fill, [4] code workspace bytes (ta_plan_* of libteam_alignment).
- * After a banded batch: pairs, chunks, 0, 0, workspace bytes. */
+ * After a banded or banded affine batch: pairs, chunks, 0, 0, workspace bytes. */
 int tm_align_plan_stats(const tm_context* ctx, uint64_t out[5]);
 
 /*
@@ -170,6 +182,9 @@ int tm_map_files_x(const char* reference_path, const char* reads_path, const tm_
 /* tm_map_files_x with a band for every window (team_mapper_amd --band N). */
 int tm_map_files_band(const char* reference_path, const char* reads_path, const tm_options* opt, const char* out_path,
                       int device, uint32_t flags, uint32_t band);
+/* ... and affine gaps (team_mapper_amd --band N --gap-open O; gap_extend = opt->gap). */
+int tm_map_files_band_affine(const char* reference_path, const char* reads_path, const tm_options* opt,
+                             const char* out_path, int device, uint32_t flags, uint32_t band, int gap_open);
 
 #ifdef __cplusplus
 }
