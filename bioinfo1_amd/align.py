@@ -174,6 +174,12 @@ def lib() -> C.CDLL:
     L.ta_banded_affine_plan_execute_traceback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.ta_banded_affine_plan_check.argtypes = [C.c_void_p]
     L.ta_banded_affine_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # exact banded alignment: the certificate and the two-round host batches
+    u8p = C.POINTER(C.c_uint8)
+    L.ta_banded_plan_certify.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ta_banded_affine_plan_certify.argtypes = L.ta_banded_plan_certify.argtypes
+    L.ta_align_batch_banded_exact.argtypes = L.ta_align_batch_banded.argtypes + [u32p, u8p]
+    L.ta_align_batch_banded_affine_exact.argtypes = L.ta_align_batch_banded_affine.argtypes + [u32p, u8p]
     # the annotate post-pass (info records, =/X CIGARs)
     L.ta_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ta_affine_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -220,6 +226,12 @@ ABI_SYMBOLS += BANDED_ABI_SYMBOLS
 # The banded affine extension's symbols (checked by tests/test_banded_affine_ref.py).
 BANDED_AFFINE_ABI_SYMBOLS = [s.replace("banded", "banded_affine") for s in BANDED_ABI_SYMBOLS]
 ABI_SYMBOLS += BANDED_AFFINE_ABI_SYMBOLS
+# Exact banded alignment's symbols (checked by tests/test_band_exact_ref.py).
+BAND_EXACT_ABI_SYMBOLS = [
+    "ta_banded_plan_certify", "ta_banded_affine_plan_certify", "ta_align_batch_banded_exact",
+    "ta_align_batch_banded_affine_exact",
+]
+ABI_SYMBOLS += BAND_EXACT_ABI_SYMBOLS
 # The drop-in C++ entry point (team_alignment.hpp), g++/libstdc++ cxx11 mangling.
 TEAM_ALIGN_SYMBOL = ("_ZN4team5AlignEPKcjS1_jNS_13AlignmentTypeEiiiPNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEEPj")
 
@@ -264,6 +276,8 @@ class BatchResult:
     cigar_offsets: np.ndarray | None  # uint64 [P]
     cigar_lens: np.ndarray | None  # uint32 [P]
     arena: np.ndarray | None  # uint8
+    band_used: np.ndarray | None = None  # uint32 [P], the exact banded entries: the band of each result
+    rounds: np.ndarray | None = None  # uint8 [P], the exact banded entries: 1 or 2
 
     def cigar(self, p: int) -> bytes | None:
         if self.arena is None:
@@ -336,7 +350,24 @@ class Aligner:
         return self._batch(batch, type, (match, mismatch, gap_open, gap_extend), want_cigar, affine=True,
                            band=_band_array(band, batch.n_pairs))
 
-    def _batch(self, batch, type, scoring, want_cigar, affine, band=None) -> BatchResult:
+    def align_batch_banded_exact(self, batch, type, match: int, mismatch: int, gap: int, band_start=None,
+                                 want_cigar: bool = True) -> BatchResult:
+        """align_batch's results at banded cost (ta_align_batch_banded_exact):
+        every pair runs at its start band (band_start: an int, one per pair,
+        or None for max(64, ceil(min(n, m) / 16))); the pairs whose score does
+        not certify their band run once more at the band that must.  The
+        result also carries band_used and rounds (1 or 2) per pair."""
+        return self._batch(batch, type, (match, mismatch, gap), want_cigar, affine=False, exact=True,
+                           band=None if band_start is None else _band_array(band_start, batch.n_pairs))
+
+    def align_batch_banded_affine_exact(self, batch, type, match: int, mismatch: int, gap_open: int, gap_extend: int,
+                                        band_start=None, want_cigar: bool = True) -> BatchResult:
+        """align_batch_affine's results at banded cost
+        (ta_align_batch_banded_affine_exact); as align_batch_banded_exact."""
+        return self._batch(batch, type, (match, mismatch, gap_open, gap_extend), want_cigar, affine=True, exact=True,
+                           band=None if band_start is None else _band_array(band_start, batch.n_pairs))
+
+    def _batch(self, batch, type, scoring, want_cigar, affine, band=None, exact=False) -> BatchResult:
         L = lib()
         t = _check_type(type)
         P = batch.n_pairs
@@ -352,18 +383,25 @@ class Aligner:
         qb = batch.qbytes if batch.qbytes.size else np.zeros(1, np.uint8)
         tbb = batch.tbytes if batch.tbytes.size else np.zeros(1, np.uint8)
         fn = L.ta_align_batch_affine if affine else L.ta_align_batch
-        extra = ()
-        if band is not None:
+        extra = tail = ()
+        used = rounds = None
+        if exact:
+            fn = L.ta_align_batch_banded_affine_exact if affine else L.ta_align_batch_banded_exact
+            extra = (None if band is None else _p(band if band.size else np.zeros(1, np.uint32), C.c_uint32),)
+            used = np.zeros(P, np.uint32)
+            rounds = np.zeros(P, np.uint8)
+            tail = (_p(used, C.c_uint32), _p(rounds, C.c_uint8))
+        elif band is not None:
             fn = L.ta_align_batch_banded_affine if affine else L.ta_align_batch_banded
             extra = (_p(band if band.size else np.zeros(1, np.uint32), C.c_uint32),)
         r = fn(
             self._h, P, qb.ctypes.data, _p(batch.qoff, C.c_uint64), _p(batch.qlen, C.c_uint32), tbb.ctypes.data,
             _p(batch.toff, C.c_uint64), _p(batch.tlen, C.c_uint32), *extra, t, *scoring, int(bool(want_cigar)),
             _p(sc, C.c_int32), _p(tb, C.c_uint32), arena.ctypes.data if want_cigar else None, cap,
-            _p(coff, C.c_uint64) if want_cigar else None, _p(clen, C.c_uint32) if want_cigar else None)
+            _p(coff, C.c_uint64) if want_cigar else None, _p(clen, C.c_uint32) if want_cigar else None, *tail)
         if r != TA_OK:
             _raise(r, self._h)
-        return BatchResult(sc, tb, coff, clen, arena)
+        return BatchResult(sc, tb, coff, clen, arena, used, rounds)
 
 
 _default: Aligner | None = None
@@ -416,6 +454,23 @@ def align_banded_affine(query: bytes, target: bytes, type, match: int, mismatch:
     _check_type(type)
     res = default_aligner().align_batch_banded_affine(from_pairs([(bytes(query), bytes(target))]), type, match,
                                                       mismatch, gap_open, gap_extend, band, want_cigar)
+    return int(res.scores[0]), res.cigar(0), int(res.target_begins[0])
+
+
+def align_banded_exact(query: bytes, target: bytes, type, match: int, mismatch: int, gap: int, band_start=None,
+                       want_cigar: bool = True, gap_open=None):
+    """Exact banded alignment for one pair -> (score, cigar bytes or None,
+    target_begin): align()'s result (gap_open=o: align_affine()'s, with
+    gap_extend = gap) computed inside a certified band."""
+    from .synth import from_pairs
+
+    _check_type(type)
+    b = from_pairs([(bytes(query), bytes(target))])
+    if gap_open is None:
+        res = default_aligner().align_batch_banded_exact(b, type, match, mismatch, gap, band_start, want_cigar)
+    else:
+        res = default_aligner().align_batch_banded_affine_exact(b, type, match, mismatch, gap_open, gap, band_start,
+                                                                want_cigar)
     return int(res.scores[0]), res.cigar(0), int(res.target_begins[0])
 
 
@@ -686,6 +741,31 @@ class DevicePlan:
         r = self._fn("ta_plan_check")(self._h)
         if r != TA_OK:
             _raise(r, self._ctx)
+
+    def certify_async(self):
+        """Banded plans: enqueue the certificate of the last run() on the
+        current stream (ta_banded[_affine]_plan_certify) -> (exact uint8,
+        band_needed int32) device tensors, allocated on first use."""
+        if not self.banded:
+            raise AttributeError("certify: not a banded plan")
+        torch = self.torch
+        if getattr(self, "exact", None) is None:
+            self.exact = torch.zeros(max(self.P, 1), dtype=torch.uint8, device=self.dev)
+            self.band_needed = torch.zeros(max(self.P, 1), dtype=torch.int32, device=self.dev)
+        r = self._fn("ta_plan_certify")(self._h, C.byref(self.io), self.exact.data_ptr(),
+                                        self.band_needed.data_ptr(), self._stream())
+        if r != TA_OK:
+            _raise(r, self._ctx)
+        return self.exact, self.band_needed
+
+    def certify(self):
+        """Banded plans, after run(): (exact, band_needed) numpy arrays [P].
+        exact[p] = 1: pair p's score, target_begin and CIGAR are the unbanded
+        ones; else band_needed[p] is the band at which they will be (where
+        exact, the pair's own clamped band)."""
+        ex, need = self.certify_async()
+        self.torch.cuda.synchronize(self.dev)
+        return ex[:self.P].cpu().numpy(), need[:self.P].cpu().numpy().view(np.uint32)
 
     def annotate(self, eqx: bool = True):
         """Enqueue the annotate pass (ta_plan_annotate) on the current stream,

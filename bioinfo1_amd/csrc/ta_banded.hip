@@ -618,6 +618,9 @@ int ta_banded_plan_execute_traceback(ta_banded_plan* pl, const ta_device_io* io,
 int ta_banded_plan_annotate(ta_banded_plan* pl, const ta_device_io* io, const ta_annotate_io* out, void* stream) {
     return ta_host::plan_annotate(pl, io, out, stream);
 }
+int ta_banded_plan_certify(ta_banded_plan* pl, const ta_device_io* io, uint8_t* exact, uint32_t* band_needed, void* stream) {
+    return ta_host::plan_certify(pl, io, 0, pl ? pl->h.gap : 0, exact, band_needed, stream);
+}
 
 int ta_align_batch_banded(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
                           const uint32_t* qlen, const char* tbytes, const uint64_t* toff, const uint32_t* tlen,

@@ -581,6 +581,10 @@ int ta_banded_affine_plan_annotate(ta_banded_affine_plan* pl, const ta_device_io
                                    void* stream) {
     return ta_host::plan_annotate(pl, io, out, stream);
 }
+int ta_banded_affine_plan_certify(ta_banded_affine_plan* pl, const ta_device_io* io, uint8_t* exact,
+                                  uint32_t* band_needed, void* stream) {
+    return ta_host::plan_certify(pl, io, pl ? pl->h.open : 0, pl ? pl->h.extend : 0, exact, band_needed, stream);
+}
 
 int ta_align_batch_banded_affine(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
                                  const uint32_t* qlen, const char* tbytes, const uint64_t* toff, const uint32_t* tlen,

@@ -145,6 +145,23 @@ struct AnnotateArgs {
     uint32_t* eqx_len;
 };
 
+// The certificate of a banded execution (ta_band_exact.hip): per pair, whether
+// its score proves the band held every optimal path, and else the band that will.
+struct BandCertifyArgs {
+    uint32_t n_pairs;
+    int mode, match, mismatch, gap_open, gap_extend;  // linear plans: gap_open = 0, gap_extend = gap
+    const uint32_t* qlen;
+    const uint32_t* tlen;
+    const uint32_t* band;        // per pair, clamped (band_clamp)
+    const uint8_t* qbytes;
+    const uint64_t* qoff;
+    const uint8_t* tbytes;
+    const uint64_t* toff;
+    const int32_t* score;        // the execution's
+    uint8_t* exact;              // [n_pairs] 1: the results are the unbanded ones
+    uint32_t* band_needed;       // [n_pairs] the band itself where exact, else ta_layout.h band_exact_needed
+};
+
 // ---- the low-latency single-pair server (ta_server.cpp, serve_kernel in ta_kernels.hip)
 // A persistent kernel, one wave per slot, serves team::Align calls posted in
 // fine-grained pinned host memory: the host writes a request (lengths,
@@ -218,6 +235,8 @@ hipError_t launch_flex_mode(const FillArgs& a, hipStream_t s);
 hipError_t launch_compact(const CompactArgs& a, hipStream_t s);
 // One wave per pair of the whole plan (ta_annotate.hip).
 hipError_t launch_annotate(const AnnotateArgs& a, hipStream_t s);
+// One wave per pair of a banded plan of either gap family (ta_band_exact.hip).
+hipError_t launch_band_certify(const BandCertifyArgs& a, hipStream_t s);
 // The server of one mode (slots waves, one per block): returns once launched.
 template <int MODE>
 hipError_t launch_serve_mode(const ServeArgs& a, uint32_t slots, hipStream_t s);

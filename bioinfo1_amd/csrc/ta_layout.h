@@ -189,6 +189,63 @@ TA_HD inline uint64_t band_swept_cells(uint32_t n, uint32_t m, uint32_t w) {
     return cells;
 }
 
+// ---- Exact banded alignment (ta_band_exact.hip; the rule is DEFINED in
+// include/team_align_c.h and restated in tests/band_exact_ref.py).  w is the
+// pair's clamped band.  Linear callers pass gap_open = 0, gap_extend = gap.
+// Arithmetic: inside the families' range rule ((n + m + 2) * max step < 2^26)
+// hs * k < 2^26, |gap_extend| * (|m - n| + 2 (w + 1)) <= |gap_extend| * (n + m)
+// < 2^26 and 2 |gap_open| < 2^27, so |U| < 2^28 and int32 would suffice; the
+// terms are formed in int64 all the same, which costs one lane a few
+// instructions and holds for any int arguments.
+TA_HD inline uint32_t band_exact_min(uint32_t n, uint32_t m) { return n < m ? n : m; }
+// Every cell in band: w >= min(n, m), or a degenerate pair.
+TA_HD inline bool band_exact_full(uint32_t n, uint32_t m, uint32_t w) {
+    return n == 0 || m == 0 || w >= band_exact_min(n, m);
+}
+// Nothing short of the full band is certified when a gap step can gain.
+TA_HD inline bool band_exact_certifiable(int gap_open, int gap_extend) { return gap_open <= 0 && gap_extend <= 0; }
+// U(w): no path that touches a diagonal outside the band scores above it.  w < min(n, m).
+TA_HD inline long long band_exact_bound(int type, uint32_t n, uint32_t m, uint32_t w, int match, int mismatch,
+                                        int gap_open, int gap_extend, uint64_t dashes) {
+    const long long hs = match > mismatch ? match : mismatch;
+    const long long k = (long long)band_exact_min(n, m) - (long long)w - 1;  // diagonal steps at the most
+    long long u = (hs > 0 ? hs : 0) * k;
+    if (type == kGlobal) {
+        const long long d = (long long)m - (long long)n;
+        const long long steps = (d < 0 ? -d : d) + 2 * ((long long)w + 1);  // gap steps at the least
+        const long long paid = steps - (long long)dashes;                  // at most `dashes` of them are free
+        u += (long long)gap_extend * (paid > 0 ? paid : 0);
+        if (dashes == 0) u += 2 * (long long)gap_open;  // one I run and one D run at the least
+    }
+    return u;
+}
+// The pair run at w scored s: is that the unbanded result?
+TA_HD inline bool band_exact_certified(int type, uint32_t n, uint32_t m, uint32_t w, int match, int mismatch,
+                                       int gap_open, int gap_extend, uint64_t dashes, long long s) {
+    if (band_exact_full(n, m, w)) return true;
+    if (!band_exact_certifiable(gap_open, gap_extend)) return false;
+    return s > band_exact_bound(type, n, m, w, match, mismatch, gap_open, gap_extend, dashes);
+}
+// needed(w, s): the smallest w' > w with U(w') < s, else min(n, m) (the full
+// band).  U does not increase with w, so a binary search finds it.  w < min(n, m).
+TA_HD inline uint32_t band_exact_needed(int type, uint32_t n, uint32_t m, uint32_t w, int match, int mismatch,
+                                        int gap_open, int gap_extend, uint64_t dashes, long long s) {
+    const uint32_t full = band_exact_min(n, m);
+    if (!band_exact_certifiable(gap_open, gap_extend)) return full;
+    uint32_t lo = w + 1, hi = full;  // the answer is in [lo, hi]; U(hi) is not asked for
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (band_exact_bound(type, n, m, mid, match, mismatch, gap_open, gap_extend, dashes) < s) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+// The start band of the host entries when the caller gives none.  A choice, not a measurement.
+TA_HD inline uint32_t band_exact_default_start(uint32_t n, uint32_t m) {
+    const uint32_t c = (band_exact_min(n, m) + 15) / 16;
+    return c > 64 ? c : 64;
+}
+
 // Upper bound on any run-length CIGAR of an n x m pair (team_alignment.cpp:145-160).
 TA_HD inline uint64_t cigar_slot_bytes(uint32_t n, uint32_t m) {
     return 2ull * ((uint64_t)n + m) + 2;

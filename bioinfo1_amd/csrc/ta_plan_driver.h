@@ -159,4 +159,26 @@ int plan_annotate(PL* pl, const ta_device_io* io, const ta_annotate_io* out, voi
     return TA_OK;
 }
 
+// Banded plans (PL derives from ta::BandArrays): enqueue the certificate of the
+// execution that wrote io->score, after it on the same stream.  Reads the
+// plan's arrays, io->score and the sequences; writes exact[P], band_needed[P].
+template <class PL>
+int plan_certify(PL* pl, const ta_device_io* io, int gap_open, int gap_extend, uint8_t* exact,
+                 uint32_t* band_needed, void* stream) {
+    if (!pl || !io) return TA_ERR_ARG;
+    ta_context* ctx = pl->ctx;
+    if (!pl->h.n_pairs) return TA_OK;
+    if (!exact || !band_needed) return fail(ctx, TA_ERR_ARG, "certify: null output");
+    if (!io->query_off || !io->target_off || !io->score) return fail(ctx, TA_ERR_ARG, "null device pointer");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    ta::BandCertifyArgs a{pl->h.n_pairs, pl->h.type, pl->h.match, pl->h.mismatch, gap_open, gap_extend,
+                          pl->d_qlen, pl->d_tlen, pl->d_band,
+                          reinterpret_cast<const uint8_t*>(io->query_bytes), io->query_off,
+                          reinterpret_cast<const uint8_t*>(io->target_bytes), io->target_off, io->score,
+                          exact, band_needed};
+    TA_HIP(ctx, ta::launch_band_certify(a, (hipStream_t)stream));
+    return TA_OK;
+}
+
 }  // namespace ta_host

@@ -16,6 +16,7 @@
 #include <utility>
 #include <vector>
 
+#include "ta_layout.h"
 #include "tm_fastx.h"
 #include "tm_internal.h"
 #include "tm_match.h"
@@ -130,7 +131,7 @@ void tm_context_destroy(tm_context* c) {
     for (tmap::DevBuf* b : {&c->bytes, &c->off, &c->len, &m.entry_off, &m.tiles, &m.hash, &m.pos, &m.keep, &m.scan,
                           &m.kept_off, &m.khash, &m.kpos, &m.cub_tmp, &c->c_off, &c->c_f, &c->c_r, &c->c_out,
                           &c->c_prev, &c->c_lis, &c->m_qoff, &c->m_toff, &c->m_score, &c->m_tb, &c->m_slots,
-                          &c->m_cstart, &c->m_clen, &c->m_coff, &c->m_cdst, &c->m_eslots, &c->m_estart, &c->m_elen, &c->m_info, &c->match.cnt_f, &c->match.cnt_r, &c->match.off_f,
+                          &c->m_cstart, &c->m_clen, &c->m_coff, &c->m_cdst, &c->m_eslots, &c->m_estart, &c->m_elen, &c->m_info, &c->m_exact, &c->m_need, &c->match.cnt_f, &c->match.cnt_r, &c->match.off_f,
                           &c->match.off_r, &c->match.key_f, &c->match.key_r, &c->match.hf, &c->match.hr,
                           &c->match.list_off, &c->match.cub_tmp})
         b->release();
@@ -231,11 +232,15 @@ int tm_map_batch(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const c
 
 // band: null = no band, the reference-exact ta_plan_*; else every window's band (ta_banded_plan_*).
 // gap_open (with a band only): affine gaps, gap_extend = opt->gap (ta_banded_affine_plan_*).
+// band_auto (band is then not read): every window at the start band of ta_layout.h
+// band_exact_default_start, certified, and the uncertified windows once more in a
+// second plan at their needed band -- the unbanded results (team_align_c.h).
 static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
                           const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
                           uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end,
                           int32_t* score, char* arena, uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
-                          uint32_t flags, ta_pair_info* info, const uint32_t* band, const int* gap_open = nullptr);
+                          uint32_t flags, ta_pair_info* info, const uint32_t* band, const int* gap_open = nullptr,
+                          bool band_auto = false);
 
 int tm_map_batch_x(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes, const uint64_t* off,
                    const uint32_t* len, const tm_options* opt, uint8_t* mapped, uint8_t* strand_fwd, uint32_t* q_begin,
@@ -263,11 +268,22 @@ int tm_map_batch_band_affine(tm_context* ctx, const tm_index* idx, uint32_t n_re
                           score, arena, arena_bytes, cigar_off, cigar_len, flags, info, &band, &gap_open);
 }
 
+int tm_map_batch_band_exact(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
+                            const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
+                            uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin,
+                            uint32_t* t_end, int32_t* score, char* arena, uint64_t arena_bytes, uint64_t* cigar_off,
+                            uint32_t* cigar_len, uint32_t flags, ta_pair_info* info, const int* gap_open) {
+    const uint32_t none = 0;
+    return map_batch_impl(ctx, idx, n_reads, bytes, off, len, opt, mapped, strand_fwd, q_begin, q_end, t_begin, t_end,
+                          score, arena, arena_bytes, cigar_off, cigar_len, flags, info, &none, gap_open, true);
+}
+
 static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
                           const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
                           uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end,
                           int32_t* score, char* arena, uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
-                          uint32_t flags, ta_pair_info* info, const uint32_t* band, const int* gap_open) {
+                          uint32_t flags, ta_pair_info* info, const uint32_t* band, const int* gap_open,
+                          bool band_auto) {
     if (!ctx || !idx || !opt) return TM_ERR_ARG;
     if (flags & ~TM_MAP_EQX) return fail(ctx, TM_ERR_ARG, "unknown flag");
     if (info && !(flags & TM_MAP_EQX)) return fail(ctx, TM_ERR_ARG, "info needs TM_MAP_EQX");
@@ -351,7 +367,7 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
         to.push_back((fwd ? 0 : idx->len) + t_begin[r]);
     }
     // 5. one alignment batch over all windows (libteam_alignment plan, device-resident)
-    const uint32_t P = (uint32_t)pair_read.size();
+    uint32_t P = (uint32_t)pair_read.size();  // (band auto: the pairs of the round that runs)
     if (!P) return TM_OK;
     ta_plan* plan = nullptr;
     ta_banded_plan* bplan = nullptr;  // with a band: the banded family instead (the same band for every window)
@@ -364,26 +380,40 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
     const uint64_t budget = hipMemGetInfo(&free_b, &total_b) == hipSuccess
                                 ? ((uint64_t)free_b + ta_context_held_bytes(ctx->ta)) / 100 * 85
                                 : 0;
+    // band auto: what a round leaves on the host instead of the caller's arrays
+    struct Round {
+        std::vector<int32_t> sc;
+        std::vector<ta_pair_info> pinfo;
+        std::vector<uint64_t> co;  // P + 1 offsets into cig
+        std::vector<char> cig;
+        std::vector<uint8_t> exact;
+        std::vector<uint32_t> need;
+    };
+    std::vector<uint32_t> bw;  // the bands of the round that runs
+    if (band) bw.assign(P, *band);
+    if (band_auto)
+        for (uint32_t p = 0; p < P; ++p) bw[p] = ta::band_exact_default_start(ql[p], tl[p]);
     int rc;
-    if (band && gap_open) {
-        const std::vector<uint32_t> bw(P, *band);
-        rc = ta_banded_affine_plan_create(ctx->ta, P, ql.data(), tl.data(), bw.data(), opt->type, opt->match,
-                                          opt->mismatch, *gap_open, opt->gap, opt->want_cigar || eqx, budget, 0,
-                                          &aplan);
-    } else if (band) {
-        const std::vector<uint32_t> bw(P, *band);
-        rc = ta_banded_plan_create(ctx->ta, P, ql.data(), tl.data(), bw.data(), opt->type, opt->match, opt->mismatch,
-                                   opt->gap, opt->want_cigar || eqx, budget, 0, &bplan);
+    auto create = [&]() -> int {  // the banded plan of either gap family over P, ql, tl, bw
+        return gap_open ? ta_banded_affine_plan_create(ctx->ta, P, ql.data(), tl.data(), bw.data(), opt->type, opt->match,
+                                                       opt->mismatch, *gap_open, opt->gap, opt->want_cigar || eqx,
+                                                       budget, 0, &aplan)
+                        : ta_banded_plan_create(ctx->ta, P, ql.data(), tl.data(), bw.data(), opt->type, opt->match,
+                                                opt->mismatch, opt->gap, opt->want_cigar || eqx, budget, 0, &bplan);
+    };
+    if (band) {
+        rc = create();
     } else {
         rc = ta_plan_create(ctx->ta, P, ql.data(), tl.data(), opt->type, opt->match, opt->mismatch, opt->gap,
                             opt->want_cigar || eqx, budget, 0, &plan);  // the annotate pass reads the CIGARs
     }
     if (rc != TA_OK) return fail(ctx, rc == TA_ERR_BAD_TYPE ? TM_ERR_BAD_TYPE : TM_ERR_DEVICE,
                                  std::string("ta_plan_create: ") + ta_last_error(ctx->ta));
-    const uint64_t slots = aplan   ? ta_banded_affine_plan_cigar_slots_bytes(aplan)
-                           : bplan ? ta_banded_plan_cigar_slots_bytes(bplan)
-                                   : ta_plan_cigar_slots_bytes(plan);
-    auto run = [&]() -> int {
+    uint64_t slots = aplan   ? ta_banded_affine_plan_cigar_slots_bytes(aplan)
+                     : bplan ? ta_banded_plan_cigar_slots_bytes(bplan)
+                             : ta_plan_cigar_slots_bytes(plan);
+    // out: null = the results go to the caller's arrays; else (band auto) a round's results and certificate
+    auto run = [&](Round* out) -> int {
         TM_HIP(ctx, ctx->m_qoff.reserve(P * 8ull));
         TM_HIP(ctx, ctx->m_toff.reserve(P * 8ull));
         TM_HIP(ctx, ctx->m_score.reserve(P * 4ull));
@@ -409,6 +439,20 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
                             : ta_plan_execute(plan, &io, s))
             return fail(ctx, TM_ERR_DEVICE, std::string("ta_plan_execute: ") + ta_last_error(ctx->ta) + " (" +
                                                 ta_status_string(r) + ")");
+        if (out) {  // the certificate, on the execution's stream
+            TM_HIP(ctx, ctx->m_exact.reserve(P));
+            TM_HIP(ctx, ctx->m_need.reserve(P * 4ull));
+            if (int r = aplan ? ta_banded_affine_plan_certify(aplan, &io, ctx->m_exact.as<uint8_t>(),
+                                                              ctx->m_need.as<uint32_t>(), s)
+                              : ta_banded_plan_certify(bplan, &io, ctx->m_exact.as<uint8_t>(),
+                                                       ctx->m_need.as<uint32_t>(), s))
+                return fail(ctx, TM_ERR_DEVICE, std::string("ta_plan_certify: ") + ta_last_error(ctx->ta) + " (" +
+                                                    ta_status_string(r) + ")");
+            out->exact.resize(P);
+            out->need.resize(P);
+            TM_HIP(ctx, hipMemcpyAsync(out->exact.data(), ctx->m_exact.p, P, hipMemcpyDeviceToHost, s));
+            TM_HIP(ctx, hipMemcpyAsync(out->need.data(), ctx->m_need.p, P * 4ull, hipMemcpyDeviceToHost, s));
+        }
         if (int r = stage(5)) return r;
         const char* c_slots = ctx->m_slots.as<const char>();
         const uint64_t* c_start = ctx->m_cstart.as<const uint64_t>();
@@ -434,7 +478,7 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
                                 : ta_plan_annotate(plan, &io, &ao, s))
                 return fail(ctx, TM_ERR_DEVICE, std::string("ta_plan_annotate: ") + ta_last_error(ctx->ta) + " (" +
                                                     ta_status_string(r) + ")");
-            if (info) {
+            if (info || out) {
                 pinfo.resize(P);
                 TM_HIP(ctx, hipMemcpyAsync(pinfo.data(), ctx->m_info.p, P * sizeof(ta_pair_info), hipMemcpyDeviceToHost, s));
             }
@@ -448,15 +492,22 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
             if (int r = tmap::compact_segments(ctx, P, c_slots, c_start, c_len, ctx->m_coff, ctx->m_cdst,
                                                ctx->match.cub_tmp, total))
                 return r;
-            if (total > arena_bytes) return fail(ctx, TM_ERR_CAPACITY, "cigar arena too small");
+            if (!out && total > arena_bytes) return fail(ctx, TM_ERR_CAPACITY, "cigar arena too small");
             co.resize(P + 1);
             TM_HIP(ctx, hipMemcpyAsync(co.data(), ctx->m_coff.p, (P + 1) * 8ull, hipMemcpyDeviceToHost, s));
-            if (total) TM_HIP(ctx, hipMemcpyAsync(arena, ctx->m_cdst.p, total, hipMemcpyDeviceToHost, s));
+            if (out) out->cig.resize(total);
+            if (total) TM_HIP(ctx, hipMemcpyAsync(out ? out->cig.data() : arena, ctx->m_cdst.p, total, hipMemcpyDeviceToHost, s));
         }
         TM_HIP(ctx, hipStreamSynchronize(s));
         if (int r = aplan ? ta_banded_affine_plan_check(aplan) : bplan ? ta_banded_plan_check(bplan) : ta_plan_check(plan))
             return fail(ctx, TM_ERR_DEVICE, std::string("ta_plan_check: ") + ta_last_error(ctx->ta) + " (" +
                                                 ta_status_string(r) + ")");
+        if (out) {  // merged below, once both rounds are in
+            out->sc.swap(sc);
+            out->pinfo.swap(pinfo);
+            out->co.swap(co);
+            return TM_OK;
+        }
         for (uint32_t p = 0; p < P; ++p) {
             const uint32_t r = pair_read[p];
             score[r] = sc[p];
@@ -474,13 +525,83 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
     ctx->plan_stats[4] = aplan   ? ta_banded_affine_plan_workspace_bytes(aplan)
                          : bplan ? ta_banded_plan_workspace_bytes(bplan)
                                  : ta_plan_workspace_bytes(plan);
-    rc = run();
+    ctx->stage_cells = 0;
+    for (uint32_t p = 0; p < P; ++p) ctx->stage_cells += (uint64_t)ql[p] * tl[p];
+    if (!band_auto) {
+        rc = run(nullptr);
+    } else {
+        // round 1 over every window, round 2 (a second plan with its own ta_device_io)
+        // over the uncertified ones; round 2's results replace round 1's
+        Round r1, r2;
+        const uint32_t P1 = P;
+        std::vector<uint32_t> again;  // round 2's k-th pair is window again[k]
+        rc = run(&r1);
+        ta_banded_plan_destroy(bplan);
+        ta_banded_affine_plan_destroy(aplan);
+        bplan = nullptr;
+        aplan = nullptr;
+        if (rc == TM_OK) {
+            std::vector<uint32_t> ql2, tl2, bw2;
+            std::vector<uint64_t> qo2, to2;
+            for (uint32_t p = 0; p < P1; ++p) {
+                if (r1.exact[p]) continue;
+                again.push_back(p);
+                ql2.push_back(ql[p]);
+                tl2.push_back(tl[p]);
+                qo2.push_back(qo[p]);
+                to2.push_back(to[p]);
+                bw2.push_back(r1.need[p]);
+            }
+            if (!again.empty()) {
+                const double ms4 = ctx->stage_ms[4], ms5 = ctx->stage_ms[5];
+                P = (uint32_t)again.size();
+                ql.swap(ql2);
+                tl.swap(tl2);
+                qo.swap(qo2);
+                to.swap(to2);
+                bw.swap(bw2);
+                rc = create();
+                if (rc != TA_OK) {
+                    rc = fail(ctx, TM_ERR_DEVICE, std::string("ta_plan_create: ") + ta_last_error(ctx->ta));
+                } else {
+                    slots = aplan ? ta_banded_affine_plan_cigar_slots_bytes(aplan) : ta_banded_plan_cigar_slots_bytes(bplan);
+                    ctx->plan_stats[1] += aplan ? ta_banded_affine_plan_chunks(aplan) : ta_banded_plan_chunks(bplan);
+                    ctx->plan_stats[4] = std::max<uint64_t>(ctx->plan_stats[4],
+                                                            aplan ? ta_banded_affine_plan_workspace_bytes(aplan)
+                                                                  : ta_banded_plan_workspace_bytes(bplan));
+                    rc = run(&r2);
+                    ctx->stage_ms[4] += ms4;  // both rounds
+                    ctx->stage_ms[5] += ms5;
+                }
+            }
+        }
+        if (rc == TM_OK) {
+            std::vector<uint32_t> slot2(P1, UINT32_MAX);
+            for (uint32_t k = 0; k < (uint32_t)again.size(); ++k) slot2[again[k]] = k;
+            uint64_t at = 0;
+            for (uint32_t p = 0; p < P1 && rc == TM_OK; ++p) {
+                const Round& R = slot2[p] == UINT32_MAX ? r1 : r2;
+                const uint32_t i = slot2[p] == UINT32_MAX ? p : slot2[p];
+                const uint32_t r = pair_read[p];
+                score[r] = R.sc[i];
+                if (info) info[r] = R.pinfo[i];
+                if (!opt->want_cigar) continue;
+                const uint64_t n = R.co[i + 1] - R.co[i];
+                if (at + n > arena_bytes) {
+                    rc = fail(ctx, TM_ERR_CAPACITY, "cigar arena too small");
+                    break;
+                }
+                std::memcpy(arena + at, R.cig.data() + R.co[i], n);
+                cigar_off[r] = at;
+                cigar_len[r] = (uint32_t)n;
+                at += n;
+            }
+        }
+    }
     ta_plan_destroy(plan);
     ta_banded_plan_destroy(bplan);
     ta_banded_affine_plan_destroy(aplan);
     if (rc == TM_OK) rc = stage(6);
-    ctx->stage_cells = 0;
-    for (uint32_t p = 0; p < P; ++p) ctx->stage_cells += (uint64_t)ql[p] * tl[p];
     return rc;
 }
 
@@ -504,7 +625,7 @@ int tm_map_files(const char* reference_path, const char* reads_path, const tm_op
 
 static int map_files_impl(const char* reference_path, const char* reads_path, const tm_options* opt,
                           const char* out_path, int device, uint32_t flags, const uint32_t* band,
-                          const int* gap_open = nullptr);
+                          const int* gap_open = nullptr, bool band_auto = false);
 
 int tm_map_files_x(const char* reference_path, const char* reads_path, const tm_options* opt, const char* out_path,
                    int device, uint32_t flags) {
@@ -521,8 +642,15 @@ int tm_map_files_band_affine(const char* reference_path, const char* reads_path,
     return map_files_impl(reference_path, reads_path, opt, out_path, device, flags, &band, &gap_open);
 }
 
+int tm_map_files_band_exact(const char* reference_path, const char* reads_path, const tm_options* opt,
+                            const char* out_path, int device, uint32_t flags, const int* gap_open) {
+    const uint32_t none = 0;
+    return map_files_impl(reference_path, reads_path, opt, out_path, device, flags, &none, gap_open, true);
+}
+
 static int map_files_impl(const char* reference_path, const char* reads_path, const tm_options* opt,
-                          const char* out_path, int device, uint32_t flags, const uint32_t* band, const int* gap_open) {
+                          const char* out_path, int device, uint32_t flags, const uint32_t* band, const int* gap_open,
+                          bool band_auto) {
     if (!reference_path || !reads_path || !opt || !out_path || (flags & ~TM_MAP_EQX)) return TM_ERR_ARG;
     const bool eqx = (flags & TM_MAP_EQX) != 0;
     tmap::FastxFile ref, reads;
@@ -580,7 +708,7 @@ static int map_files_impl(const char* reference_path, const char* reads_path, co
         std::vector<ta_pair_info> info(eqx ? nr : 0);
         rc = map_batch_impl(ctx, idx, nr, reads.seq.data() + base, off.data(), len.data(), &o, mapped.data(),
                             fwd.data(), qb.data(), qe.data(), tb.data(), te.data(), sc.data(), arena.data(), arena.size(),
-                            co.data(), cl.data(), flags, eqx ? info.data() : nullptr, band, gap_open);
+                            co.data(), cl.data(), flags, eqx ? info.data() : nullptr, band, gap_open, band_auto);
         if (rc) {
             std::fprintf(stderr, "map: %s: %s\n", tm_status_string(rc), tm_last_error(ctx));
             break;

@@ -92,6 +92,7 @@ struct tm_context {
     // tm_map_batch
     tmap::DevBuf m_qoff, m_toff, m_score, m_tb, m_slots, m_cstart, m_clen, m_coff, m_cdst;
     tmap::DevBuf m_eslots, m_estart, m_elen, m_info;  // TM_MAP_EQX: the annotate pass's outputs
+    tmap::DevBuf m_exact, m_need;  // band auto: the certificate of a round (ta_banded[_affine]_plan_certify)
     double stage_ms[tmap::kStages] = {};
     uint64_t stage_cells = 0;
     uint64_t plan_stats[5] = {};  // tm_align_plan_stats

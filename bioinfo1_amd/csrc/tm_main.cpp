@@ -41,6 +41,7 @@ int main(int argc, char** argv) {
     unsigned flags = 0;  // --eqx: =/X CIGARs and an NM tag (not in help(), which restates the reference's text)
     bool banded = false;  // --band N: every window through the banded extension (not in help() either)
     unsigned band = 0;
+    bool band_auto = false;  // --band auto: a certified band per window, the unbanded results (not in help() either)
     bool affine = false;  // --gap-open O (with --band): affine gaps, -g is the gap extend (not in help() either)
     int gap_open = 0;
     if (argc < 2) {
@@ -82,6 +83,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(a, "-d") && more) device = std::atoi(argv[++i]);
         else if (!std::strcmp(a, "-c")) o.want_cigar = 1;
         else if (!std::strcmp(a, "--eqx")) flags |= TM_MAP_EQX;
+        else if (!std::strcmp(a, "--band") && more && !std::strcmp(argv[i + 1], "auto")) {
+            ++i;
+            banded = band_auto = true;
+        }
         else if (!std::strcmp(a, "--band") && more) {
             char* end = nullptr;
             const unsigned long long v = std::strtoull(argv[++i], &end, 10);
@@ -90,6 +95,7 @@ int main(int argc, char** argv) {
                 return 1;
             }
             banded = true;
+            band_auto = false;
             band = (unsigned)v;
         }
         else if (!std::strcmp(a, "--gap-open") && more) {
@@ -121,7 +127,9 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "Error: --gap-open requires --band (there is no unbanded affine mapper path)\n");
         return 1;
     }
-    const int r = affine   ? tm_map_files_band_affine(f1.c_str(), f2.c_str(), &o, "-", device, flags, band, gap_open)
+    const int r = band_auto ? tm_map_files_band_exact(f1.c_str(), f2.c_str(), &o, "-", device, flags,
+                                                      affine ? &gap_open : nullptr)
+                  : affine   ? tm_map_files_band_affine(f1.c_str(), f2.c_str(), &o, "-", device, flags, band, gap_open)
                   : banded ? tm_map_files_band(f1.c_str(), f2.c_str(), &o, "-", device, flags, band)
                            : tm_map_files_x(f1.c_str(), f2.c_str(), &o, "-", device, flags);
     if (r != TM_OK && r != TM_ERR_INPUT) std::fprintf(stderr, "error: %s\n", tm_status_string(r));

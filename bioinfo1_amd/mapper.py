@@ -33,7 +33,7 @@ ABI_SYMBOLS = ["tm_status_string", "tm_last_error", "tm_context_create", "tm_con
                "tm_minimize_batch", "tm_chain_batch", "tm_index_create", "tm_index_destroy", "tm_index_stats",
                "tm_map_batch", "tm_stage_times", "tm_align_plan_stats", "tm_map_files", "tm_map_batch_x",
                "tm_map_files_x", "tm_map_batch_band", "tm_map_files_band", "tm_map_batch_band_affine",
-               "tm_map_files_band_affine"]
+               "tm_map_files_band_affine", "tm_map_batch_band_exact", "tm_map_files_band_exact"]
 TM_MAP_EQX = 1
 
 _lib = None
@@ -87,6 +87,8 @@ def lib() -> C.CDLL:
     L.tm_map_files_band.argtypes = L.tm_map_files_x.argtypes + [C.c_uint32]
     L.tm_map_batch_band_affine.argtypes = L.tm_map_batch_band.argtypes + [C.c_int]
     L.tm_map_files_band_affine.argtypes = L.tm_map_files_band.argtypes + [C.c_int]
+    L.tm_map_batch_band_exact.argtypes = L.tm_map_batch_x.argtypes + [C.POINTER(C.c_int)]  # gap_open, nullable
+    L.tm_map_files_band_exact.argtypes = L.tm_map_files_x.argtypes + [C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -259,11 +261,16 @@ class Index:
         band: None, or the band of every window (tm_map_batch_band: the banded
         extension instead of the reference-exact plan).
         gap_open: None, or (with a band) the gap open of the banded affine
-        extension (tm_map_batch_band_affine; opt.gap is the gap extend)."""
+        extension (tm_map_batch_band_affine; opt.gap is the gap extend).
+        band="auto": a certified band per window (tm_map_batch_band_exact) --
+        the results of band=None; with gap_open, of unbanded affine gaps."""
         L = lib()
         if gap_open is not None and band is None:
             raise ValueError("gap_open needs a band: the mapper has no unbanded affine path")
-        if band is not None and not 0 <= int(band) <= 0xFFFFFFFF:
+        auto = isinstance(band, str)
+        if auto and band != "auto":
+            raise ValueError("band: a number in [0, 2^32) or 'auto'")
+        if band is not None and not auto and not 0 <= int(band) <= 0xFFFFFFFF:
             raise ValueError("band: must be in [0, 2^32)")
         b, off, ln = _soa(reads)
         n = len(ln)
@@ -274,14 +281,19 @@ class Index:
         arena = np.zeros(max(cap, 1), np.uint8)
         if band is not None:
             info = np.zeros(n, _align.PAIR_INFO_DTYPE) if eqx else None
-            fn, more = (L.tm_map_batch_band, ()) if gap_open is None else (L.tm_map_batch_band_affine, (int(gap_open),))
+            if auto:
+                fn, more = L.tm_map_batch_band_exact, (None if gap_open is None else C.byref(C.c_int(int(gap_open))),)
+            elif gap_open is None:
+                fn, more = L.tm_map_batch_band, (int(band),)
+            else:
+                fn, more = L.tm_map_batch_band_affine, (int(band), int(gap_open))
             _check(fn(self.mapper._h, self._h, n, b.ctypes.data, _p(off, C.c_uint64),
                       _p(ln, C.c_uint32), C.byref(opt), _p(out["mapped"], C.c_uint8),
                       _p(out["strand_fwd"], C.c_uint8), _p(out["q_begin"], C.c_uint32),
                       _p(out["q_end"], C.c_uint32), _p(out["t_begin"], C.c_uint32),
                       _p(out["t_end"], C.c_uint32), _p(out["scores"], C.c_int32), arena.ctypes.data,
                       cap, _p(out["cigar_off"], C.c_uint64), _p(out["cigar_len"], C.c_uint32),
-                      TM_MAP_EQX if eqx else 0, info.ctypes.data if eqx else None, int(band), *more),
+                      TM_MAP_EQX if eqx else 0, info.ctypes.data if eqx else None, *more),
                    self.mapper._h)
             return MapResult(arena=arena, info=info, **out)
         if eqx:
@@ -316,10 +328,17 @@ class Index:
 
 def map_files(reference: str, reads: str, out: str = "-", device: int = 0, band=None, gap_open=None, **opts) -> None:
     """The whole mapper on files, in process (tm_map_files; band: tm_map_files_band;
-    band and gap_open: tm_map_files_band_affine, gap being the gap extend)."""
+    band and gap_open: tm_map_files_band_affine, gap being the gap extend;
+    band="auto": tm_map_files_band_exact, the unbanded results)."""
     o = Options.make(**opts)
     if gap_open is not None and band is None:
         raise ValueError("gap_open needs a band: the mapper has no unbanded affine path")
+    if isinstance(band, str):
+        if band != "auto":
+            raise ValueError("band: a number in [0, 2^32) or 'auto'")
+        _check(lib().tm_map_files_band_exact(reference.encode(), reads.encode(), C.byref(o), out.encode(), device, 0,
+                                             None if gap_open is None else C.byref(C.c_int(int(gap_open)))))
+        return
     if band is not None:
         if not 0 <= int(band) <= 0xFFFFFFFF:
             raise ValueError("band: must be in [0, 2^32)")

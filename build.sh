@@ -58,6 +58,8 @@ cc "$B/ta_affine.o" "$CS/ta_affine.hip" "$HIPCC" "${FLAGS[@]}" -c "$CS/ta_affine
 cc "$B/ta_banded.o" "$CS/ta_banded.hip" "$HIPCC" "${FLAGS[@]}" -c "$CS/ta_banded.hip"
 # banded affine extension; its kernels' resource usage (VGPRs, scratch) goes to the build log as remarks
 cc "$B/ta_banded_affine.o" "$CS/ta_banded_affine.hip" "$HIPCC" "${FLAGS[@]}" -Rpass-analysis=kernel-resource-usage -c "$CS/ta_banded_affine.hip"
+# exact banded alignment (the certify kernel and the two-round host batches); resource usage to the build log
+cc "$B/ta_band_exact.o" "$CS/ta_band_exact.hip" "$HIPCC" "${FLAGS[@]}" -Rpass-analysis=kernel-resource-usage -c "$CS/ta_band_exact.hip"
 cc "$B/ta_api.o" "$CS/ta_api.hip" "$HIPCC" "${FLAGS[@]}" -c "$CS/ta_api.hip"
 cc "$B/ta_server.o" "$CS/ta_server.cpp" "$HIPCC" "${FLAGS[@]}" -x hip -c "$CS/ta_server.cpp"
 cc "$B/shim.o" "$CS/team_alignment_shim.cpp" "$HIPCC" "${FLAGS[@]}" -x c++ -c "$CS/team_alignment_shim.cpp"
@@ -77,7 +79,7 @@ done
 cc "$B/tm_main.o" "$CS/tm_main.cpp" "$HIPCC" "${FLAGS[@]}" -x c++ -c "$CS/tm_main.cpp"
 fi
 for p in "${pids[@]}"; do wait "$p"; done
-"$HIPCC" -shared -fPIC --offload-arch=gfx950 "$B"/ta_fill_{0,1,2}{0,1}.o "$B"/ta_dual_{0,1,2}{0,1}.o "$B/ta_dual_blk.o" "$B"/ta_dual_ck_{0,1,2}.o "$B/ta_walk_ck.o" "$B"/ta_flex_{0,1,2}{0,1}.o "$B"/ta_flex_ck_{0,1,2}.o "$B/ta_misc.o" "$B/ta_annotate.o" "$B/ta_affine.o" "$B/ta_banded.o" "$B/ta_banded_affine.o" "$B/ta_api.o" "$B/ta_server.o" "$B/ta_planner.o" "$B/ta_pipeline.o" "$B/shim.o" \
+"$HIPCC" -shared -fPIC --offload-arch=gfx950 "$B"/ta_fill_{0,1,2}{0,1}.o "$B"/ta_dual_{0,1,2}{0,1}.o "$B/ta_dual_blk.o" "$B"/ta_dual_ck_{0,1,2}.o "$B/ta_walk_ck.o" "$B"/ta_flex_{0,1,2}{0,1}.o "$B"/ta_flex_ck_{0,1,2}.o "$B/ta_misc.o" "$B/ta_annotate.o" "$B/ta_affine.o" "$B/ta_banded.o" "$B/ta_banded_affine.o" "$B/ta_band_exact.o" "$B/ta_api.o" "$B/ta_server.o" "$B/ta_planner.o" "$B/ta_pipeline.o" "$B/shim.o" \
   -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib -o "$OUT"
 if [ "${TA_LIB_ONLY:-0}" = 1 ]; then echo "built $OUT"; exit 0; fi
 PKG="$ROOT/bioinfo1_amd"

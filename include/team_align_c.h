@@ -567,6 +567,72 @@ int ta_align_batch_banded_affine(ta_context* ctx, uint32_t n_pairs, const char* 
                                  int32_t* score, uint32_t* target_begin, char* cigar_arena,
                                  uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len);
 
+/*
+ * ---- Exact banded alignment: a banded execution certifies, pair by pair,
+ * that its band held every optimal path -- its results are then the unbanded
+ * ones byte for byte -- and an uncertified pair names the band that will.
+ * Nothing above changes behaviour.
+ *
+ * Definition, for a pair of lengths n, m, its band w (clamped to max(n, m)),
+ * the scoring, and hs = max(match, mismatch).  Linear gaps read gap_open = 0,
+ * gap_extend = gap below.
+ *   Full band.  If w >= min(n, m) every cell is in band; the same holds for a
+ *     degenerate pair (n == 0 or m == 0).  The pair is exact.
+ *   Uncertifiable scoring.  If gap > 0 (affine: gap_open > 0 or
+ *     gap_extend > 0) nothing is certified short of the full band.
+ *   Bound.  Every path that leaves the band crosses diagonal hi + 1 or lo - 1,
+ *     and such a path takes at most k = min(n, m) - w - 1 diagonal steps.
+ *       Local and semi-global:  U(w) = max(hs, 0) * k.
+ *       Global linear:  U(w) = max(hs, 0) * k
+ *                              + gap * max(0, |m - n| + 2 (w + 1) - dashes):
+ *         such a path takes at least |m - n| + 2 (w + 1) gap steps; dashes is
+ *         the number of '-' bytes in both sequences, and at most that many
+ *         gap steps are free.
+ *       Global affine:  gap -> gap_extend, plus 2 * gap_open when dashes == 0
+ *         (the path needs at least one I run and one D run).
+ *   Certified means score_banded(w) > U(w); the comparison is strict.
+ *   Needed band.  needed(w, s) is the smallest w' > w with U(w') < s; if there
+ *     is none below min(n, m), it is min(n, m).  U does not increase with w.
+ *   Two rounds always suffice: a banded score never falls when the band grows,
+ *     so the pair run at needed(w0, score(w0)) is certified.
+ * ta_layout.h band_exact_bound / band_exact_needed evaluate the rule on the
+ * host and in the kernel; tests/band_exact_ref.py restates it.
+ */
+
+/* After an execution of `plan` into io, on the same stream: exact_dev[p] = 1
+ * when pair p is certified (its score, target_begin and CIGAR are the unbanded
+ * ones) else 0; band_needed_dev[p] = the pair's clamped band where exact, else
+ * needed(band, score).  Reads the plan's arrays, io->score and the sequences. */
+int ta_banded_plan_certify(ta_banded_plan* plan, const ta_device_io* io, uint8_t* exact_dev,
+                           uint32_t* band_needed_dev, void* hip_stream);
+int ta_banded_affine_plan_certify(ta_banded_affine_plan* plan, const ta_device_io* io, uint8_t* exact_dev,
+                                  uint32_t* band_needed_dev, void* hip_stream);
+
+/* Host-memory batches with the unbanded results at banded cost:
+ * ta_align_batch_banded[_affine] run at band_start[p] (NULL: the start rule
+ * max(64, ceil(min(n, m) / 16)) -- a choice, not a measurement), certified,
+ * and the uncertified pairs run once more at their needed band, as one banded
+ * batch over gathered offsets into the same byte buffers.  For every pair the
+ * score, target_begin and CIGAR equal ta_align_batch's (linear) or
+ * ta_align_batch_affine's; the outputs are laid out as ta_align_batch_banded
+ * lays them out (CIGARs back to back in pair order).  band_used (optional):
+ * the clamped band each result was computed at; rounds (optional): 1 or 2.
+ * Errors are the banded entries'. */
+int ta_align_batch_banded_exact(ta_context* ctx, uint32_t n_pairs, const char* query_bytes,
+                                const uint64_t* query_off, const uint32_t* query_len, const char* target_bytes,
+                                const uint64_t* target_off, const uint32_t* target_len, const uint32_t* band_start,
+                                int type, int match, int mismatch, int gap, int want_cigar, int32_t* score,
+                                uint32_t* target_begin, char* cigar_arena, uint64_t cigar_arena_bytes,
+                                uint64_t* cigar_off, uint32_t* cigar_len, uint32_t* band_used, uint8_t* rounds);
+int ta_align_batch_banded_affine_exact(ta_context* ctx, uint32_t n_pairs, const char* query_bytes,
+                                       const uint64_t* query_off, const uint32_t* query_len,
+                                       const char* target_bytes, const uint64_t* target_off,
+                                       const uint32_t* target_len, const uint32_t* band_start, int type, int match,
+                                       int mismatch, int gap_open, int gap_extend, int want_cigar, int32_t* score,
+                                       uint32_t* target_begin, char* cigar_arena, uint64_t cigar_arena_bytes,
+                                       uint64_t* cigar_off, uint32_t* cigar_len, uint32_t* band_used,
+                                       uint8_t* rounds);
+
 #ifdef __cplusplus
 }
 #endif

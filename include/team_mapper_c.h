@@ -154,6 +154,22 @@ int tm_map_batch_band_affine(tm_context* ctx, const tm_index* idx, uint32_t n_re
                              uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags, ta_pair_info* info,
                              uint32_t band, int gap_open);
 
+/* tm_map_batch_x's results at banded cost (exact banded alignment,
+ * team_align_c.h): every window runs at the start band
+ * max(64, ceil(min(n, m) / 16)) and is certified on the device
+ * (ta_banded[_affine]_plan_certify); the uncertified windows run once more, in
+ * a second plan at their needed band, and the rounds are merged before the
+ * results are written.  gap_open NULL: linear gaps, every output equals
+ * tm_map_batch_x's.  gap_open non-NULL: affine gaps with gap_extend = opt->gap,
+ * the results of an unbanded affine alignment of every window.  Stage times
+ * [4] and [5] hold both rounds; the plan stats count both plans' chunks. */
+int tm_map_batch_band_exact(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
+                            const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
+                            uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin,
+                            uint32_t* t_end, int32_t* score, char* cigar_arena, uint64_t cigar_arena_bytes,
+                            uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags, ta_pair_info* info,
+                            const int* gap_open);
+
 /* Wall time (ms) of the last tm_map_batch on this context, per stage:
  * [0] read upload, [1] minimizers, [2] seed matching, [3] FindLIS chaining,
  * [4] windows + alignment plan (host), [5] alignment (fill + traceback),
@@ -185,6 +201,10 @@ int tm_map_files_band(const char* reference_path, const char* reads_path, const 
 /* ... and affine gaps (team_mapper_amd --band N --gap-open O; gap_extend = opt->gap). */
 int tm_map_files_band_affine(const char* reference_path, const char* reads_path, const tm_options* opt,
                              const char* out_path, int device, uint32_t flags, uint32_t band, int gap_open);
+/* tm_map_files_x through tm_map_batch_band_exact (team_mapper_amd --band auto): with gap_open NULL the
+ * output is tm_map_files_x's byte for byte; with --gap-open O, unbanded-exact affine mapping. */
+int tm_map_files_band_exact(const char* reference_path, const char* reads_path, const tm_options* opt,
+                            const char* out_path, int device, uint32_t flags, const int* gap_open);
 
 #ifdef __cplusplus
 }
