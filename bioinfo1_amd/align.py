@@ -180,6 +180,27 @@ def lib() -> C.CDLL:
     L.ta_banded_affine_plan_certify.argtypes = L.ta_banded_plan_certify.argtypes
     L.ta_align_batch_banded_exact.argtypes = L.ta_align_batch_banded.argtypes + [u32p, u8p]
     L.ta_align_batch_banded_affine_exact.argtypes = L.ta_align_batch_banded_affine.argtypes + [u32p, u8p]
+    # anchored (free-end) alignment (include/team_align_c.h, no reference counterpart)
+    L.ta_align_batch_anchored.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, u64p, u32p, C.c_void_p, u64p, u32p, u32p,
+                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i32p, u32p, u32p, C.c_void_p,
+                                          C.c_uint64, u64p, u32p]
+    L.ta_anchored_plan_create.argtypes = [C.c_void_p, C.c_uint32, u32p, u32p, u32p, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ta_anchored_plan_destroy.argtypes = [C.c_void_p]
+    L.ta_anchored_plan_destroy.restype = None
+    for f in ("ta_anchored_plan_cigar_slots_bytes", "ta_anchored_plan_workspace_bytes",
+              "ta_anchored_plan_band_cells", "ta_anchored_plan_swept_cells"):
+        getattr(L, f).restype = C.c_uint64
+        getattr(L, f).argtypes = [C.c_void_p]
+    L.ta_anchored_plan_chunks.restype = C.c_uint32
+    L.ta_anchored_plan_chunks.argtypes = [C.c_void_p]
+    L.ta_anchored_plan_pair_chunks.argtypes = [C.c_void_p, u32p]
+    L.ta_anchored_plan_execute.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ta_anchored_plan_execute_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ta_anchored_plan_execute_traceback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ta_anchored_plan_check.argtypes = [C.c_void_p]
+    L.ta_anchored_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ta_anchored_plan_ends.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # the annotate post-pass (info records, =/X CIGARs)
     L.ta_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ta_affine_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -232,6 +253,10 @@ BAND_EXACT_ABI_SYMBOLS = [
     "ta_align_batch_banded_affine_exact",
 ]
 ABI_SYMBOLS += BAND_EXACT_ABI_SYMBOLS
+# Anchored (free-end) alignment's symbols (checked by tests/test_anchored_ref.py).
+ANCHORED_ABI_SYMBOLS = [s.replace("banded", "anchored") for s in BANDED_ABI_SYMBOLS] + ["ta_anchored_plan_ends"]
+ABI_SYMBOLS += ANCHORED_ABI_SYMBOLS
+TA_ANCHORED_AFFINE_KERNELS = 1  # ta_anchored_plan_create flag: the affine kernels even at gap_open == 0
 # The drop-in C++ entry point (team_alignment.hpp), g++/libstdc++ cxx11 mangling.
 TEAM_ALIGN_SYMBOL = ("_ZN4team5AlignEPKcjS1_jNS_13AlignmentTypeEiiiPNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEEPj")
 
@@ -278,6 +303,8 @@ class BatchResult:
     arena: np.ndarray | None  # uint8
     band_used: np.ndarray | None = None  # uint32 [P], the exact banded entries: the band of each result
     rounds: np.ndarray | None = None  # uint8 [P], the exact banded entries: 1 or 2
+    query_ends: np.ndarray | None = None  # uint32 [P], the anchored entries: the goal cell's row
+    target_ends: np.ndarray | None = None  # uint32 [P], ... and its column
 
     def cigar(self, p: int) -> bytes | None:
         if self.arena is None:
@@ -367,6 +394,40 @@ class Aligner:
         return self._batch(batch, type, (match, mismatch, gap_open, gap_extend), want_cigar, affine=True, exact=True,
                            band=None if band_start is None else _band_array(band_start, batch.n_pairs))
 
+    def align_batch_anchored(self, batch, match: int, mismatch: int, gap: int, band, gap_open: int = 0,
+                             want_cigar: bool = True) -> BatchResult:
+        """Anchored (free-end) alignment (ta_align_batch_anchored): every path
+        starts at (0, 0) and ends at the best in-band interior cell, or stays
+        at (0, 0) with score 0 when none is positive.  band: an int or one
+        per pair.  gap_open == 0: linear gaps; else affine with gap_extend =
+        gap.  The result carries query_ends / target_ends (the goal cells);
+        target_begins is all 0."""
+        L = lib()
+        P = batch.n_pairs
+        bd = _band_array(band, P)
+        sc = np.zeros(P, np.int32)
+        qe = np.zeros(P, np.uint32)
+        te = np.zeros(P, np.uint32)
+        coff = clen = arena = None
+        cap = 0
+        if want_cigar:
+            cap = int((2 * (batch.qlen.astype(np.uint64) + batch.tlen.astype(np.uint64)) + 2).sum()) if P else 0
+            arena = np.zeros(max(cap, 1), np.uint8)
+            coff = np.zeros(P, np.uint64)
+            clen = np.zeros(P, np.uint32)
+        qb = batch.qbytes if batch.qbytes.size else np.zeros(1, np.uint8)
+        tbb = batch.tbytes if batch.tbytes.size else np.zeros(1, np.uint8)
+        r = L.ta_align_batch_anchored(
+            self._h, P, qb.ctypes.data, _p(batch.qoff, C.c_uint64), _p(batch.qlen, C.c_uint32), tbb.ctypes.data,
+            _p(batch.toff, C.c_uint64), _p(batch.tlen, C.c_uint32),
+            _p(bd if bd.size else np.zeros(1, np.uint32), C.c_uint32), match, mismatch, gap_open, gap,
+            int(bool(want_cigar)), _p(sc, C.c_int32), _p(qe, C.c_uint32), _p(te, C.c_uint32),
+            arena.ctypes.data if want_cigar else None, cap, _p(coff, C.c_uint64) if want_cigar else None,
+            _p(clen, C.c_uint32) if want_cigar else None)
+        if r != TA_OK:
+            _raise(r, self._h)
+        return BatchResult(sc, np.zeros(P, np.uint32), coff, clen, arena, query_ends=qe, target_ends=te)
+
     def _batch(self, batch, type, scoring, want_cigar, affine, band=None, exact=False) -> BatchResult:
         L = lib()
         t = _check_type(type)
@@ -455,6 +516,16 @@ def align_banded_affine(query: bytes, target: bytes, type, match: int, mismatch:
     res = default_aligner().align_batch_banded_affine(from_pairs([(bytes(query), bytes(target))]), type, match,
                                                       mismatch, gap_open, gap_extend, band, want_cigar)
     return int(res.scores[0]), res.cigar(0), int(res.target_begins[0])
+
+
+def align_anchored(query: bytes, target: bytes, match: int, mismatch: int, gap: int, band: int, gap_open: int = 0,
+                   want_cigar: bool = True):
+    """Anchored alignment for one pair -> (score, cigar bytes or None, query_end, target_end)."""
+    from .synth import from_pairs
+
+    res = default_aligner().align_batch_anchored(from_pairs([(bytes(query), bytes(target))]), match, mismatch, gap,
+                                                 band, gap_open, want_cigar)
+    return int(res.scores[0]), res.cigar(0), int(res.query_ends[0]), int(res.target_ends[0])
 
 
 def align_banded_exact(query: bytes, target: bytes, type, match: int, mismatch: int, gap: int, band_start=None,
@@ -608,7 +679,7 @@ class DevicePlan:
 
     def __init__(self, aligner: Aligner, batch, type, match, mismatch, gap, want_cigar=True, device=None,
                  workspace_budget: int = 0, gap_open=None, flags: int = 0, inputs=None, records=None, band=None,
-                 _banded_affine: bool = False):
+                 _banded_affine: bool = False, _anchored: bool = False):
         """gap_open=None: team::Align's linear gap.  gap_open=o: the affine-gap
         extension (ta_affine_plan_*) with gap_extend = gap.  flags: TA_PLAN_*
         kernel selection (tests / measurements; same results).  inputs: the
@@ -625,14 +696,15 @@ class DevicePlan:
             raise ValueError("band and gap_open cannot be combined here: the banded extension is linear-gap only; "
                              "use DevicePlan.banded_affine(...) for the banded affine extension")
         L = lib()
-        t = _check_type(type)
+        t = () if _anchored else (_check_type(type),)  # (the anchored family takes no type)
         self.torch = torch
         self.dev = torch.device("cuda", aligner.device) if device is None else device
         self.P = batch.n_pairs
         self.want_cigar = bool(want_cigar)
         self.affine = gap_open is not None
         self.banded = band is not None
-        family = ("ta_banded_affine_plan_" if self.affine and self.banded else
+        self.anchored = _anchored
+        family = ("ta_anchored_plan_" if _anchored else "ta_banded_affine_plan_" if self.affine and self.banded else
                   "ta_affine_plan_" if self.affine else "ta_banded_plan_" if self.banded else "ta_plan_")
         self._fn = lambda name: getattr(L, name.replace("ta_plan_", family))
         h = C.c_void_p()
@@ -642,7 +714,7 @@ class DevicePlan:
             self.band = _band_array(band, self.P)
             extra = (_p(self.band if self.band.size else np.zeros(1, np.uint32), C.c_uint32),)
         r = self._fn("ta_plan_create")(aligner.handle, self.P, _p(batch.qlen, C.c_uint32),
-                                       _p(batch.tlen, C.c_uint32), *extra, t, *scoring, int(self.want_cigar),
+                                       _p(batch.tlen, C.c_uint32), *extra, *t, *scoring, int(self.want_cigar),
                                        workspace_budget, flags, C.byref(h))
         if r != TA_OK:
             _raise(r, aligner.handle)
@@ -690,6 +762,42 @@ class DevicePlan:
         pair.  The other arguments as the constructor's."""
         return cls(aligner, batch, type, match, mismatch, gap_extend, want_cigar, device, workspace_budget,
                    gap_open=gap_open, inputs=inputs, records=records, band=band, _banded_affine=True)
+
+    @classmethod
+    def anchored(cls, aligner: Aligner, batch, match, mismatch, gap, band, gap_open: int = 0, want_cigar=True,
+                 workspace_budget: int = 0, flags: int = 0, device=None, inputs=None, records=None):
+        """A plan of anchored (free-end) alignment (ta_anchored_plan_*): every
+        path starts at (0, 0) and ends at the best in-band interior cell.
+        band: an int, or one per pair.  gap_open == 0: the linear kernels
+        (flags=TA_ANCHORED_AFFINE_KERNELS: the affine ones); else affine gaps
+        with gap_extend = gap.  run / results / annotate / pair_chunks /
+        band_cells / swept_cells as on a banded plan; ends() returns the goal
+        cells; certify() raises."""
+        return cls(aligner, batch, None, match, mismatch, gap, want_cigar, device, workspace_budget,
+                   gap_open=int(gap_open), flags=flags, inputs=inputs, records=records, band=band,
+                   _banded_affine=True, _anchored=True)
+
+    def ends_async(self):
+        """Anchored plans: enqueue the copy of the last run()'s goal cells on the
+        current stream (ta_anchored_plan_ends) -> (query_end, target_end)
+        int32 device tensors, allocated on first use."""
+        if not self.anchored:
+            raise AttributeError("ends: not an anchored plan")
+        torch = self.torch
+        if getattr(self, "query_end", None) is None:
+            self.query_end = torch.zeros(max(self.P, 1), dtype=torch.int32, device=self.dev)
+            self.target_end = torch.zeros(max(self.P, 1), dtype=torch.int32, device=self.dev)
+        r = lib().ta_anchored_plan_ends(self._h, self.query_end.data_ptr(), self.target_end.data_ptr(),
+                                        self._stream())
+        if r != TA_OK:
+            _raise(r, self._ctx)
+        return self.query_end, self.target_end
+
+    def ends(self):
+        """Anchored plans, after run() or the fills: (query_end, target_end) uint32 numpy arrays [P]."""
+        qe, te = self.ends_async()
+        self.torch.cuda.synchronize(self.dev)
+        return qe[:self.P].cpu().numpy().view(np.uint32), te[:self.P].cpu().numpy().view(np.uint32)
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
@@ -748,6 +856,8 @@ class DevicePlan:
         band_needed int32) device tensors, allocated on first use."""
         if not self.banded:
             raise AttributeError("certify: not a banded plan")
+        if self.anchored:
+            raise AttributeError("certify: certification does not cover anchored plans")
         torch = self.torch
         if getattr(self, "exact", None) is None:
             self.exact = torch.zeros(max(self.P, 1), dtype=torch.uint8, device=self.dev)

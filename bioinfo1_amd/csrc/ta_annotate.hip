@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void annotate_kernel(AnnotateArgs a) {
     if (p >= a.n_pairs) return;
     const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.qlen[p]);
     const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.tlen[p]);
-    // the goal cell: analytic where no cell exists (n or m 0: local (0, 0), semi-global (0, m))
+    // the goal cell: analytic where no cell exists (n or m 0: local and anchored (0, 0), semi-global (0, m))
     uint32_t gi = n, gj = m;
     if (a.mode != kGlobal) {
         gi = 0;
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(kBlock) void annotate_kernel(AnnotateArgs a) {
         } else if (a.mode == kLocal) {  // the ends minus the consumption
             r.query_begin = i0;
             r.target_begin = j0;
-        } else {  // the cell after the free leading run
+        } else {  // the cell after the free leading run (kAnchored comes here too: no free run, so 0 / 0)
             r.query_begin = first_op == 'D' ? lead_cnt : 0u;
             r.target_begin = first_op == 'I' ? lead_cnt : 0u;
         }

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/team_align_c.h"
+#include "ta_anchored.h"
 #include "ta_context.h"
 #include "ta_device.h"
 #include "ta_host_batch.h"
@@ -80,8 +81,9 @@ __device__ __forceinline__ PassOut band_pass(const BandArgs& a, const uint8_t* Q
                                              uint32_t m, uint32_t w, uint32_t pass, bool last_pass, uint32_t* prow,
                                              int32_t* B, int lane) {
     constexpr int R = kRows;
+    constexpr bool ARGMAX = MODE == kLocal || MODE == kAnchored;  // the goal is the best interior cell
     const int gap = a.gap, MA = a.match, MI = a.mismatch;
-    const int init = (MODE == kGlobal) ? gap : 0;  // :58-74
+    const int init = (MODE == kGlobal || MODE == kAnchored) ? gap : 0;  // :58-74
     const int lo = band_lo(n, m, w), hi = band_hi(n, m, w);
     const uint32_t BW = (uint32_t)(hi - lo);
     const uint32_t row_base = pass * kPassRows;
@@ -122,7 +124,7 @@ __device__ __forceinline__ PassOut band_pass(const BandArgs& a, const uint8_t* Q
         else if (lane == 0) recv = B[c0 - 1];  // (c0 > 1 only below pass 0: the previous pass's bottom row)
     }
     int kc[R];  // local argmax key = 16 h + (15 - r) on valid rows
-    if constexpr (MODE == kLocal) {
+    if constexpr (ARGMAX) {
 #pragma unroll
         for (int r = 0; r < R; ++r) kc[r] = (uint32_t)r < vlim ? (R - 1 - r) : -(1 << 30);
     }
@@ -205,14 +207,17 @@ __device__ __forceinline__ PassOut band_pass(const BandArgs& a, const uint8_t* Q
                     accI = shl1_add_lanebit(accI, imask);
                 }
                 if (MASKED) h = ((uint32_t)(e - r) <= BW) ? h : kSent;  // off the band: no cell
-                if (MODE == kLocal) {  // (kSent << 4 would wrap: an out-of-band cell keys as h = -1)
-                    const int hk = MASKED ? max(h, -1) : h;
+                // (kSent << 4 would wrap: an out-of-band cell keys as h = -1.  Anchored: no clamp, so in
+                // every step -- the padding rows below row n can fall below -2^26 -- each h <= 0 keys
+                // as -1; only h > 0 can move the goal)
+                if (ARGMAX) {
+                    const int hk = (MASKED || MODE == kAnchored) ? max(h, -1) : h;
                     stepkey = max(stepkey, (int)(((uint32_t)hk << 4) + (uint32_t)kc[r]));
                 }
                 H[r] = h;
                 upv = h;
             });
-            if (MODE == kLocal) {
+            if (ARGMAX) {
                 if (stepkey > bestkey) {  // strict: the first column keeps a tie (:186)
                     bestkey = stepkey;
                     bestj = (uint32_t)j;
@@ -243,7 +248,7 @@ __device__ __forceinline__ PassOut band_pass(const BandArgs& a, const uint8_t* Q
     for (; t < steps; ++t) step(t, std::true_type{});
 
     PassOut o{kFloor, 0, 0, kFloor, 0, 0};
-    if (MODE == kLocal) {
+    if (ARGMAX) {
         // h first over lanes (the row tag only orders rows inside a lane), then the first lane
         const int hk = (uint32_t)lane < nl ? (bestkey >> 4) : INT_MIN;
         const int mx = wave_max(hk);
@@ -280,8 +285,9 @@ __device__ __forceinline__ PassOut band_pass(const BandArgs& a, const uint8_t* Q
     return o;
 }
 
+// (the anchored score-only fill is held to the local one's waves per SIMD; 0: no bound)
 template <int MODE, bool CIGAR>
-__global__ __launch_bounds__(kBlock) void banded_fill_kernel(BandArgs a) {
+__global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 4 : 0) void banded_fill_kernel(BandArgs a) {
     const int lane = threadIdx.x & 63;
     const uint32_t widx = wave_id();
     if (widx >= a.count) return;  // wave-uniform
@@ -299,6 +305,7 @@ __global__ __launch_bounds__(kBlock) void banded_fill_kernel(BandArgs a) {
                 score = n ? wmul(n, a.gap) : wmul(m, a.gap);
             } else if (MODE == kLocal) {
                 tb = 1;
+            } else if (MODE == kAnchored) {  // the goal stays at (0, 0)
             } else {
                 gj = (n == 0) ? m : 0;
             }
@@ -317,7 +324,8 @@ __global__ __launch_bounds__(kBlock) void banded_fill_kernel(BandArgs a) {
     const int lo = band_lo(n, m, w), hi = band_hi(n, m, w);
 
     // semi: the column scan starts at (0, m) (cost 0) where that cell is in band
-    int best_h = (MODE == kSemi && (int)m <= hi) ? 0 : kFloor;
+    // anchored: the scan starts at (0, 0) (cost 0), and only an interior cell above it moves the goal
+    int best_h = ((MODE == kSemi && (int)m <= hi) || MODE == kAnchored) ? 0 : kFloor;
     uint32_t best_i = 0, best_j = (MODE == kSemi) ? m : 0;
     int corner = 0;
     for (uint32_t pass = 0; pass < passes; ++pass) {
@@ -482,6 +490,7 @@ hipError_t launch_banded_fill(int mode, bool cigar, const BandArgs& a, hipStream
         TA_BAND_FILL(kGlobal)
         TA_BAND_FILL(kLocal)
         TA_BAND_FILL(kSemi)
+        TA_BAND_FILL(kAnchored)
         default: return hipErrorInvalidValue;
     }
 #undef TA_BAND_FILL
@@ -492,7 +501,10 @@ hipError_t launch_banded_traceback(int mode, const BandArgs& a, hipStream_t s) {
     if (a.count == 0) return hipSuccess;
     const dim3 g = band_grid(a.count), b(kBlock);
     switch (mode) {
-        case kGlobal: hipLaunchKernelGGL(banded_traceback_kernel<kGlobal>, g, b, 0, s, a); break;
+        case kGlobal:
+        case kAnchored:  // the global walk, from the anchored goal to row / column 0
+            hipLaunchKernelGGL(banded_traceback_kernel<kGlobal>, g, b, 0, s, a);
+            break;
         case kLocal: hipLaunchKernelGGL(banded_traceback_kernel<kLocal>, g, b, 0, s, a); break;
         case kSemi: hipLaunchKernelGGL(banded_traceback_kernel<kSemi>, g, b, 0, s, a); break;
         default: return hipErrorInvalidValue;
@@ -648,3 +660,55 @@ int ta_align_batch_banded(ta_context* ctx, uint32_t n_pairs, const char* qb, con
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// The anchored family's linear half (ta_anchored.h): this family's plan in
+// Mode kAnchored.  The arguments are checked as a global plan's.
+namespace ta_host {
+
+int anchored_linear_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
+                           const uint32_t* band, int match, int mismatch, int gap, int want_cigar, uint64_t budget,
+                           ta_banded_plan** out) {
+    if (!out) return TA_ERR_ARG;
+    *out = nullptr;
+    if (int r = band_check_args(ctx, n_pairs, qlen, tlen, band, TA_GLOBAL, match, mismatch, gap)) return r;
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    auto* pl = new ta_banded_plan();
+    pl->ctx = ctx;
+    ta::build_band_plan(pl->h, n_pairs, qlen, tlen, band, ta::kAnchored, match, mismatch, gap, want_cigar != 0,
+                        budget ? budget : default_budget(ctx));
+    return plan_create_block(pl, "ta_anchored_plan_create: ", out);
+}
+
+int anchored_linear_ends(ta_banded_plan* pl, uint32_t* query_end_dev, uint32_t* target_end_dev, void* stream) {
+    return plan_ends(pl, query_end_dev, target_end_dev, stream);
+}
+
+int anchored_linear_batch(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
+                          const uint32_t* qlen, const char* tbytes, const uint64_t* toff, const uint32_t* tlen,
+                          const uint32_t* band, int match, int mismatch, int gap, int want_cigar, int32_t* score,
+                          uint32_t* query_end, uint32_t* target_end, char* arena, uint64_t arena_bytes,
+                          uint64_t* cigar_off, uint32_t* cigar_len) {
+    uint64_t qend = 0, tend = 0;
+    if (int r = check_host_batch(ctx, TA_GLOBAL, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, want_cigar, arena,
+                                 cigar_off, cigar_len, &qend, &tend))
+        return r;
+    if (n_pairs == 0) return TA_OK;
+    if (int r = band_check_args(ctx, n_pairs, qlen, tlen, band, TA_GLOBAL, match, mismatch, gap)) return r;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    ta_banded_plan pl;
+    pl.ctx = ctx;
+    uint64_t need = 0;
+    if (want_cigar)
+        for (uint32_t p = 0; p < n_pairs; ++p) need += 4 * ta::band_ptr_dwords(qlen[p], tlen[p], band[p]);
+    // everything in one chunk while the codes take at most 1 GiB (no device query per call)
+    const uint64_t budget = need <= (1ull << 30) ? std::max<uint64_t>(need, 1) : default_budget(ctx);
+    ta::build_band_plan(pl.h, n_pairs, qlen, tlen, band, ta::kAnchored, match, mismatch, gap, want_cigar != 0, budget);
+    if (int r = host_batch(ctx, pl, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
+                           nullptr, arena, arena_bytes, cigar_off, cigar_len))
+        return r;
+    return batch_ends(ctx, pl, query_end, target_end);
+}
+
+}  // namespace ta_host

@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "../../include/team_align_c.h"
+#include "ta_anchored.h"
 #include "ta_context.h"
 #include "ta_device.h"
 #include "ta_host_batch.h"
@@ -90,6 +91,7 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
                                                  uint32_t m, uint32_t w, uint32_t pass, bool last_pass, uint2* prow,
                                                  int2* B, int lane) {
     constexpr int R = kRows;
+    constexpr bool ARGMAX = MODE == kLocal || MODE == kAnchored;  // the goal is the best interior cell
     const int O = a.open, X = a.extend, OX = wadd(a.open, a.extend);
     const int MA = a.match, MI = a.mismatch;
     const int lo = band_lo(n, m, w), hi = band_hi(n, m, w);
@@ -106,7 +108,7 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
     const uint8_t* Tc = T + (c0 - 1);  // the byte of column c0 + k is Tc[k]
     auto in_band = [&](int d) { return (uint32_t)(d - lo) <= BW; };
     // H of a boundary cell (row 0 or column 0) L steps from (0, 0), where in band
-    auto edge = [&](uint32_t L) { return (MODE == kGlobal && L) ? wadd(O, wmul(L, X)) : 0; };
+    auto edge = [&](uint32_t L) { return ((MODE == kGlobal || MODE == kAnchored) && L) ? wadd(O, wmul(L, X)) : 0; };
 
     uint32_t qp[R / 4];  // the lane's 16 query bytes, 4 per register
 #pragma unroll
@@ -146,7 +148,7 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
     }
     int recvF = kSent, Flast = kSent;
     int kc[R];  // local argmax key = 16 h + (15 - r) on valid rows
-    if constexpr (MODE == kLocal) {
+    if constexpr (ARGMAX) {
 #pragma unroll
         for (int r = 0; r < R; ++r) kc[r] = (uint32_t)r < vlim ? (R - 1 - r) : -(1 << 30);
     }
@@ -238,8 +240,11 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
                     ev = inb ? ev : kSent;
                     f = inb ? f : kSent;
                 }
-                if constexpr (MODE == kLocal) {  // (kSent << 4 would wrap: an out-of-band cell keys as h = -1)
-                    const int hk = MASKED ? max(h, -1) : h;
+                // (kSent << 4 would wrap: an out-of-band cell keys as h = -1.  Anchored: no clamp, so in
+                // every step -- the padding rows below row n can fall below -2^26 -- each h <= 0 keys
+                // as -1; only h > 0 can move the goal)
+                if constexpr (ARGMAX) {
+                    const int hk = (MASKED || MODE == kAnchored) ? max(h, -1) : h;
                     stepkey = max(stepkey, (int)(((uint32_t)hk << 4) + (uint32_t)kc[r]));
                 }
                 E[r] = ev;
@@ -248,7 +253,7 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
                 upF = f;
             });
             Flast = upF;
-            if constexpr (MODE == kLocal) {
+            if constexpr (ARGMAX) {
                 if (stepkey > bestkey) {  // strict: the first column keeps a tie (:186)
                     bestkey = stepkey;
                     bestj = (uint32_t)j;
@@ -281,7 +286,7 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
     for (; t < steps; ++t) step(t, std::true_type{});
 
     PassOut o{kFloor, 0, 0, kFloor, 0, 0};
-    if constexpr (MODE == kLocal) {
+    if constexpr (ARGMAX) {
         // h first over lanes (the row tag only orders rows inside a lane), then the first lane
         const int hk = (uint32_t)lane < nl ? (bestkey >> 4) : INT_MIN;
         const int mx = wave_max(hk);
@@ -318,8 +323,9 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
     return o;
 }
 
+// (the anchored score-only fill is held to the local one's waves per SIMD; 0: no bound)
 template <int MODE, bool CIGAR>
-__global__ __launch_bounds__(kBlock) void banded_affine_fill_kernel(BandAffArgs a) {
+__global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 3 : 0) void banded_affine_fill_kernel(BandAffArgs a) {
     const int lane = threadIdx.x & 63;
     const uint32_t widx = wave_id();
     if (widx >= a.count) return;  // wave-uniform
@@ -337,6 +343,7 @@ __global__ __launch_bounds__(kBlock) void banded_affine_fill_kernel(BandAffArgs 
                 score = (n || m) ? wadd(a.open, wmul(n ? n : m, a.extend)) : 0;
             } else if (MODE == kLocal) {
                 tb = 1;
+            } else if (MODE == kAnchored) {  // the goal stays at (0, 0)
             } else {
                 gj = (n == 0) ? m : 0;
             }
@@ -355,7 +362,8 @@ __global__ __launch_bounds__(kBlock) void banded_affine_fill_kernel(BandAffArgs 
     const int lo = band_lo(n, m, w), hi = band_hi(n, m, w);
 
     // semi: the column scan starts at (0, m) (cost 0) where that cell is in band
-    int best_h = (MODE == kSemi && (int)m <= hi) ? 0 : kFloor;
+    // anchored: the scan starts at (0, 0) (cost 0), and only an interior cell above it moves the goal
+    int best_h = ((MODE == kSemi && (int)m <= hi) || MODE == kAnchored) ? 0 : kFloor;
     uint32_t best_i = 0, best_j = (MODE == kSemi) ? m : 0;
     int corner = 0;
     for (uint32_t pass = 0; pass < passes; ++pass) {
@@ -436,6 +444,7 @@ hipError_t launch_banded_affine_fill(int mode, bool cigar, const BandAffArgs& a,
         TA_BAND_AFF_FILL(kGlobal)
         TA_BAND_AFF_FILL(kLocal)
         TA_BAND_AFF_FILL(kSemi)
+        TA_BAND_AFF_FILL(kAnchored)
         default: return hipErrorInvalidValue;
     }
 #undef TA_BAND_AFF_FILL
@@ -446,7 +455,10 @@ hipError_t launch_banded_affine_traceback(int mode, const BandAffArgs& a, hipStr
     if (a.count == 0) return hipSuccess;
     const dim3 g = band_aff_grid(a.count), b(kBlock);
     switch (mode) {
-        case kGlobal: hipLaunchKernelGGL(banded_affine_traceback_kernel<kGlobal>, g, b, 0, s, a); break;
+        case kGlobal:
+        case kAnchored:  // the global three-state walk, from the anchored goal to row / column 0
+            hipLaunchKernelGGL(banded_affine_traceback_kernel<kGlobal>, g, b, 0, s, a);
+            break;
         case kLocal: hipLaunchKernelGGL(banded_affine_traceback_kernel<kLocal>, g, b, 0, s, a); break;
         case kSemi: hipLaunchKernelGGL(banded_affine_traceback_kernel<kSemi>, g, b, 0, s, a); break;
         default: return hipErrorInvalidValue;
@@ -614,3 +626,58 @@ int ta_align_batch_banded_affine(ta_context* ctx, uint32_t n_pairs, const char* 
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// The anchored family's affine half (ta_anchored.h): this family's plan in
+// Mode kAnchored.  The arguments are checked as a global plan's.
+namespace ta_host {
+
+int anchored_affine_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
+                           const uint32_t* band, int match, int mismatch, int gap_open, int gap_extend, int want_cigar,
+                           uint64_t budget, ta_banded_affine_plan** out) {
+    if (!out) return TA_ERR_ARG;
+    *out = nullptr;
+    if (int r = band_aff_check_args(ctx, n_pairs, qlen, tlen, band, TA_GLOBAL, match, mismatch, gap_open, gap_extend))
+        return r;
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    auto* pl = new ta_banded_affine_plan();
+    pl->ctx = ctx;
+    ta::build_band_affine_plan(pl->h, n_pairs, qlen, tlen, band, ta::kAnchored, match, mismatch, gap_open, gap_extend,
+                               want_cigar != 0, budget ? budget : default_budget(ctx));
+    return plan_create_block(pl, "ta_anchored_plan_create: ", out);
+}
+
+int anchored_affine_ends(ta_banded_affine_plan* pl, uint32_t* query_end_dev, uint32_t* target_end_dev, void* stream) {
+    return plan_ends(pl, query_end_dev, target_end_dev, stream);
+}
+
+int anchored_affine_batch(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
+                          const uint32_t* qlen, const char* tbytes, const uint64_t* toff, const uint32_t* tlen,
+                          const uint32_t* band, int match, int mismatch, int gap_open, int gap_extend, int want_cigar,
+                          int32_t* score, uint32_t* query_end, uint32_t* target_end, char* arena,
+                          uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len) {
+    uint64_t qend = 0, tend = 0;
+    if (int r = check_host_batch(ctx, TA_GLOBAL, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, want_cigar, arena,
+                                 cigar_off, cigar_len, &qend, &tend))
+        return r;
+    if (n_pairs == 0) return TA_OK;
+    if (int r = band_aff_check_args(ctx, n_pairs, qlen, tlen, band, TA_GLOBAL, match, mismatch, gap_open, gap_extend))
+        return r;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    ta_banded_affine_plan pl;
+    pl.ctx = ctx;
+    uint64_t need = 0;
+    if (want_cigar)
+        for (uint32_t p = 0; p < n_pairs; ++p) need += sizeof(uint2) * ta::band_ptr_dwords(qlen[p], tlen[p], band[p]);
+    // everything in one chunk while the codes take at most 1 GiB (no device query per call)
+    const uint64_t budget = need <= (1ull << 30) ? std::max<uint64_t>(need, 1) : default_budget(ctx);
+    ta::build_band_affine_plan(pl.h, n_pairs, qlen, tlen, band, ta::kAnchored, match, mismatch, gap_open, gap_extend,
+                               want_cigar != 0, budget);
+    if (int r = host_batch(ctx, pl, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
+                           nullptr, arena, arena_bytes, cigar_off, cigar_len))
+        return r;
+    return batch_ends(ctx, pl, query_end, target_end);
+}
+
+}  // namespace ta_host

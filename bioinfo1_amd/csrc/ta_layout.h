@@ -22,7 +22,9 @@ constexpr int kPassRows = kRows * kWave;
 constexpr int kWavesPerBlock = 4;
 constexpr int kBlock = kWave * kWavesPerBlock;
 
-enum Mode : int { kGlobal = 0, kLocal = 1, kSemi = 2 };
+// kAnchored (the ta_anchored_* family only; never a caller's AlignmentType):
+// global boundaries and recurrence, the goal at the best in-band interior cell.
+enum Mode : int { kGlobal = 0, kLocal = 1, kSemi = 2, kAnchored = 3 };
 
 // Local dual fill (ta_dual.hip) with three-input maxima: its biased values
 // S = 16H + z*j - i and every candidate, shifted by the returned offset, lie in

@@ -181,4 +181,31 @@ int plan_certify(PL* pl, const ta_device_io* io, int gap_open, int gap_extend, u
     return TA_OK;
 }
 
+// Anchored plans (a banded family's plan built in Mode kAnchored): enqueue the
+// copy of the last execution's goal cells, after it on the same stream.
+template <class PL>
+int plan_ends(PL* pl, uint32_t* query_end_dev, uint32_t* target_end_dev, void* stream) {
+    if (!pl) return TA_ERR_ARG;
+    ta_context* ctx = pl->ctx;
+    if (!pl->h.n_pairs) return TA_OK;
+    if (!query_end_dev || !target_end_dev) return fail(ctx, TA_ERR_ARG, "ends: null output");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = 4ull * pl->h.n_pairs;
+    TA_HIP(ctx, hipMemcpyAsync(query_end_dev, pl->d_goal_i, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    TA_HIP(ctx, hipMemcpyAsync(target_end_dev, pl->d_goal_j, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return TA_OK;
+}
+
+// ... and after a host batch (its stream drained, ctx->mu still held): the goal cells to host arrays.
+template <class PL>
+int batch_ends(ta_context* ctx, const PL& pl, uint32_t* query_end, uint32_t* target_end) {
+    const size_t bytes = 4ull * pl.h.n_pairs;
+    hipStream_t s = ctx->stream;
+    if (query_end) TA_HIP(ctx, hipMemcpyAsync(query_end, pl.d_goal_i, bytes, hipMemcpyDeviceToHost, s));
+    if (target_end) TA_HIP(ctx, hipMemcpyAsync(target_end, pl.d_goal_j, bytes, hipMemcpyDeviceToHost, s));
+    TA_HIP(ctx, hipStreamSynchronize(s));
+    return TA_OK;
+}
+
 }  // namespace ta_host

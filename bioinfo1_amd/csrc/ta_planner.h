@@ -153,6 +153,7 @@ struct BandPlan : PlanBase {
 };
 
 // budget = bytes of 2-bit codes per chunk (> 0); band[p] is clamped to its pair (ta_layout.h band_clamp).
+// type: a Mode of ta_layout.h, kAnchored included (sized as global: codes, boundary rows, chunks, slots).
 void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
                      int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget);
 

@@ -20,6 +20,7 @@
 #include "tm_fastx.h"
 #include "tm_internal.h"
 #include "tm_match.h"
+#include "tm_stitch.h"
 
 struct tm_index {
     tm_context* ctx = nullptr;
@@ -131,7 +132,8 @@ void tm_context_destroy(tm_context* c) {
     for (tmap::DevBuf* b : {&c->bytes, &c->off, &c->len, &m.entry_off, &m.tiles, &m.hash, &m.pos, &m.keep, &m.scan,
                           &m.kept_off, &m.khash, &m.kpos, &m.cub_tmp, &c->c_off, &c->c_f, &c->c_r, &c->c_out,
                           &c->c_prev, &c->c_lis, &c->m_qoff, &c->m_toff, &c->m_score, &c->m_tb, &c->m_slots,
-                          &c->m_cstart, &c->m_clen, &c->m_coff, &c->m_cdst, &c->m_eslots, &c->m_estart, &c->m_elen, &c->m_info, &c->m_exact, &c->m_need, &c->match.cnt_f, &c->match.cnt_r, &c->match.off_f,
+                          &c->m_cstart, &c->m_clen, &c->m_coff, &c->m_cdst, &c->m_eslots, &c->m_estart, &c->m_elen, &c->m_info, &c->m_exact, &c->m_need, &c->e_qoff, &c->e_toff, &c->e_score, &c->e_tb, &c->e_slots, &c->e_cstart, &c->e_clen,
+                          &c->e_qend, &c->e_tend, &c->e_meta, &c->e_rev, &c->match.cnt_f, &c->match.cnt_r, &c->match.off_f,
                           &c->match.off_r, &c->match.key_f, &c->match.key_r, &c->match.hf, &c->match.hr,
                           &c->match.list_off, &c->match.cub_tmp})
         b->release();
@@ -235,12 +237,14 @@ int tm_map_batch(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const c
 // band_auto (band is then not read): every window at the start band of ta_layout.h
 // band_exact_default_start, certified, and the uncertified windows once more in a
 // second plan at their needed band -- the unbanded results (team_align_c.h).
+// extend_ends (a numeric band, global type, no TM_MAP_EQX): each window is then extended
+// to the read's ends by two anchored alignments and the three CIGARs are stitched.
 static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
                           const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
                           uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end,
                           int32_t* score, char* arena, uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
                           uint32_t flags, ta_pair_info* info, const uint32_t* band, const int* gap_open = nullptr,
-                          bool band_auto = false);
+                          bool band_auto = false, bool extend_ends = false);
 
 int tm_map_batch_x(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes, const uint64_t* off,
                    const uint32_t* len, const tm_options* opt, uint8_t* mapped, uint8_t* strand_fwd, uint32_t* q_begin,
@@ -268,6 +272,20 @@ int tm_map_batch_band_affine(tm_context* ctx, const tm_index* idx, uint32_t n_re
                           score, arena, arena_bytes, cigar_off, cigar_len, flags, info, &band, &gap_open);
 }
 
+uint64_t tm_ends_arena_extra(uint32_t len, uint32_t band) {
+    const uint64_t cap = 3ull * len + 6;
+    return 4ull * (band < cap ? band : cap) + 4;
+}
+
+int tm_map_batch_band_ends(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
+                           const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
+                           uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end,
+                           int32_t* score, char* arena, uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
+                           uint32_t flags, ta_pair_info* info, uint32_t band, const int* gap_open) {
+    return map_batch_impl(ctx, idx, n_reads, bytes, off, len, opt, mapped, strand_fwd, q_begin, q_end, t_begin, t_end,
+                          score, arena, arena_bytes, cigar_off, cigar_len, flags, info, &band, gap_open, false, true);
+}
+
 int tm_map_batch_band_exact(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
                             const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
                             uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin,
@@ -283,11 +301,16 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
                           uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end,
                           int32_t* score, char* arena, uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
                           uint32_t flags, ta_pair_info* info, const uint32_t* band, const int* gap_open,
-                          bool band_auto) {
+                          bool band_auto, bool extend_ends) {
     if (!ctx || !idx || !opt) return TM_ERR_ARG;
     if (flags & ~TM_MAP_EQX) return fail(ctx, TM_ERR_ARG, "unknown flag");
     if (info && !(flags & TM_MAP_EQX)) return fail(ctx, TM_ERR_ARG, "info needs TM_MAP_EQX");
     const bool eqx = (flags & TM_MAP_EQX) != 0;
+    if (extend_ends) {  // (the annotate records of the three pieces are not stitched)
+        if (!band || band_auto) return fail(ctx, TM_ERR_ARG, "--extend-ends needs a numeric band");
+        if (opt->type != TA_GLOBAL) return fail(ctx, TM_ERR_ARG, "--extend-ends needs the global alignment type");
+        if (eqx) return fail(ctx, TM_ERR_ARG, "--extend-ends cannot be combined with TM_MAP_EQX");
+    }
     if (opt->type != TA_GLOBAL && opt->type != TA_LOCAL && opt->type != TA_SEMI_GLOBAL)
         return fail(ctx, TM_ERR_BAD_TYPE, tm_status_string(TM_ERR_BAD_TYPE));
     if (opt->k != idx->k || opt->w != idx->w) return fail(ctx, TM_ERR_ARG, "k/w differ from the index");
@@ -312,6 +335,12 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
         ctx->stage_ms[i] = std::chrono::duration<double, std::milli>(t - t_last).count();
         ctx->stage_ms[tmap::kStages - 1] = std::chrono::duration<double, std::milli>(t - t_first).count();
         t_last = t;
+        return TM_OK;
+    };
+    auto stage_add = [&](int i) -> int {  // ... or add to it (a stage that runs in two parts)
+        const double before = ctx->stage_ms[i];
+        if (int r = stage(i)) return r;
+        ctx->stage_ms[i] += before;
         return TM_OK;
     };
     if (nbytes) TM_HIP(ctx, hipMemcpyAsync(ctx->bytes.p, bytes, nbytes, hipMemcpyHostToDevice, s));
@@ -439,7 +468,7 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
                             : ta_plan_execute(plan, &io, s))
             return fail(ctx, TM_ERR_DEVICE, std::string("ta_plan_execute: ") + ta_last_error(ctx->ta) + " (" +
                                                 ta_status_string(r) + ")");
-        if (out) {  // the certificate, on the execution's stream
+        if (out && band_auto) {  // the certificate, on the execution's stream
             TM_HIP(ctx, ctx->m_exact.reserve(P));
             TM_HIP(ctx, ctx->m_need.reserve(P * 4ull));
             if (int r = aplan ? ta_banded_affine_plan_certify(aplan, &io, ctx->m_exact.as<uint8_t>(),
@@ -527,7 +556,154 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
                                  : ta_plan_workspace_bytes(plan);
     ctx->stage_cells = 0;
     for (uint32_t p = 0; p < P; ++p) ctx->stage_cells += (uint64_t)ql[p] * tl[p];
-    if (!band_auto) {
+    // --extend-ends: one end (right: in place; left: the reversed bytes) of every window through an
+    // anchored plan with a ta_device_io of its own -> scores, goal cells and CIGARs on the host
+    struct End {
+        std::vector<int32_t> sc;
+        std::vector<uint32_t> gi, gj;
+        std::vector<uint64_t> co;  // P + 1 offsets into cig
+        std::vector<char> cig;
+    };
+    auto run_end = [&](const uint32_t* eq, const uint32_t* et, const char* qbytes, const uint64_t* d_qoff,
+                       const char* tbytes, const uint64_t* d_toff, End& out) -> int {
+        struct Guard {
+            ta_anchored_plan* p = nullptr;
+            ~Guard() { ta_anchored_plan_destroy(p); }
+        } g;
+        const std::vector<uint32_t> ebw(P, *band);
+        if (ta_anchored_plan_create(ctx->ta, P, eq, et, ebw.data(), opt->match, opt->mismatch, gap_open ? *gap_open : 0,
+                                    opt->gap, opt->want_cigar, budget, 0, &g.p) != TA_OK)
+            return fail(ctx, TM_ERR_DEVICE, std::string("ta_anchored_plan_create: ") + ta_last_error(ctx->ta));
+        const uint64_t eslots = ta_anchored_plan_cigar_slots_bytes(g.p);
+        ctx->plan_stats[1] += ta_anchored_plan_chunks(g.p);
+        ctx->plan_stats[4] = std::max<uint64_t>(ctx->plan_stats[4], ta_anchored_plan_workspace_bytes(g.p));
+        TM_HIP(ctx, ctx->e_score.reserve(P * 4ull));
+        TM_HIP(ctx, ctx->e_tb.reserve(P * 4ull));
+        TM_HIP(ctx, ctx->e_cstart.reserve(P * 8ull));
+        TM_HIP(ctx, ctx->e_clen.reserve(P * 4ull));
+        TM_HIP(ctx, ctx->e_slots.reserve(eslots + 1));
+        TM_HIP(ctx, ctx->e_qend.reserve(P * 4ull));
+        TM_HIP(ctx, ctx->e_tend.reserve(P * 4ull));
+        ta_device_io io{};
+        io.query_bytes = qbytes;
+        io.query_off = d_qoff;
+        io.target_bytes = tbytes;
+        io.target_off = d_toff;
+        io.score = ctx->e_score.as<int32_t>();
+        io.target_begin = ctx->e_tb.as<uint32_t>();
+        io.cigar_slots = ctx->e_slots.as<char>();
+        io.cigar_start = ctx->e_cstart.as<uint64_t>();
+        io.cigar_len = ctx->e_clen.as<uint32_t>();
+        int r = ta_anchored_plan_execute(g.p, &io, s);
+        if (r == TA_OK) r = ta_anchored_plan_ends(g.p, ctx->e_qend.as<uint32_t>(), ctx->e_tend.as<uint32_t>(), s);
+        if (r != TA_OK)
+            return fail(ctx, TM_ERR_DEVICE, std::string("ta_anchored_plan_execute: ") + ta_last_error(ctx->ta) + " (" +
+                                                ta_status_string(r) + ")");
+        out.sc.resize(P);
+        out.gi.resize(P);
+        out.gj.resize(P);
+        TM_HIP(ctx, hipMemcpyAsync(out.sc.data(), ctx->e_score.p, P * 4ull, hipMemcpyDeviceToHost, s));
+        TM_HIP(ctx, hipMemcpyAsync(out.gi.data(), ctx->e_qend.p, P * 4ull, hipMemcpyDeviceToHost, s));
+        TM_HIP(ctx, hipMemcpyAsync(out.gj.data(), ctx->e_tend.p, P * 4ull, hipMemcpyDeviceToHost, s));
+        if (opt->want_cigar) {
+            uint64_t total = 0;
+            if (int rr = tmap::compact_segments(ctx, P, io.cigar_slots, io.cigar_start, io.cigar_len, ctx->m_coff,
+                                                ctx->m_cdst, ctx->match.cub_tmp, total))
+                return rr;
+            out.co.resize(P + 1);
+            out.cig.resize(total);
+            TM_HIP(ctx, hipMemcpyAsync(out.co.data(), ctx->m_coff.p, (P + 1) * 8ull, hipMemcpyDeviceToHost, s));
+            if (total) TM_HIP(ctx, hipMemcpyAsync(out.cig.data(), ctx->m_cdst.p, total, hipMemcpyDeviceToHost, s));
+        }
+        TM_HIP(ctx, hipStreamSynchronize(s));
+        return TM_OK;
+    };
+    // the windows' results are in `mid`; extends q/t begin/end, sums the scores, stitches the CIGARs
+    auto extend = [&](const Round& mid) -> int {
+        const uint64_t L = idx->len;
+        const uint64_t w = *band;
+        // right ends: query R[qe+1 .. len), target S[te+1 .. te+1+mr), mr = min(L-1-te, nr + w), read in place
+        std::vector<uint32_t> eq(P), et(P);
+        std::vector<uint64_t> eqo(P), eto(P);
+        for (uint32_t p = 0; p < P; ++p) {
+            const uint32_t r = pair_read[p];
+            const uint64_t strand = strand_fwd[r] ? 0 : L;
+            eq[p] = len[r] - 1 - q_end[r];
+            et[p] = (uint32_t)std::min<uint64_t>(L - 1 - t_end[r], eq[p] + w);
+            eqo[p] = off[r] + q_end[r] + 1;
+            eto[p] = strand + t_end[r] + 1;
+        }
+        TM_HIP(ctx, ctx->e_qoff.reserve(P * 8ull));
+        TM_HIP(ctx, ctx->e_toff.reserve(P * 8ull));
+        TM_HIP(ctx, hipMemcpyAsync(ctx->e_qoff.p, eqo.data(), P * 8ull, hipMemcpyHostToDevice, s));
+        TM_HIP(ctx, hipMemcpyAsync(ctx->e_toff.p, eto.data(), P * 8ull, hipMemcpyHostToDevice, s));
+        End right, left;
+        if (int r = run_end(eq.data(), et.data(), ctx->bytes.as<const char>(), ctx->e_qoff.as<const uint64_t>(),
+                            idx->ref2.as<const char>(), ctx->e_toff.as<const uint64_t>(), right))
+            return r;
+        // left ends: the reverse of R[0 .. qb) against the reverse of S[tb-ml .. tb), ml = min(tb, nl + w),
+        // gathered into a staging buffer: [queries][targets], one offset array each
+        std::vector<uint64_t> meta(4ull * P);  // source ends (q, t), then staging offsets (q, t)
+        uint64_t at = 0;
+        for (uint32_t p = 0; p < P; ++p) {
+            const uint32_t r = pair_read[p];
+            eq[p] = q_begin[r];
+            et[p] = (uint32_t)std::min<uint64_t>(t_begin[r], eq[p] + w);
+            meta[p] = off[r] + q_begin[r];
+            meta[P + p] = (strand_fwd[r] ? 0 : L) + t_begin[r];
+            meta[2ull * P + p] = at;
+            at += eq[p];
+        }
+        for (uint32_t p = 0; p < P; ++p) {
+            meta[3ull * P + p] = at;
+            at += et[p];
+        }
+        TM_HIP(ctx, ctx->e_meta.reserve(4ull * P * 8 + 2ull * P * 4));
+        TM_HIP(ctx, ctx->e_rev.reserve(at + 1));
+        uint64_t* d_meta = ctx->e_meta.as<uint64_t>();
+        uint32_t* d_lens = reinterpret_cast<uint32_t*>(d_meta + 4ull * P);
+        TM_HIP(ctx, hipMemcpyAsync(d_meta, meta.data(), 4ull * P * 8, hipMemcpyHostToDevice, s));
+        TM_HIP(ctx, hipMemcpyAsync(d_lens, eq.data(), P * 4ull, hipMemcpyHostToDevice, s));
+        TM_HIP(ctx, hipMemcpyAsync(d_lens + P, et.data(), P * 4ull, hipMemcpyHostToDevice, s));
+        if (int r = tmap::reverse_gather(ctx, P, ctx->bytes.as<const uint8_t>(), d_meta, d_lens, d_meta + 2ull * P,
+                                         ctx->e_rev.as<uint8_t>()))
+            return r;
+        if (int r = tmap::reverse_gather(ctx, P, idx->ref2.as<const uint8_t>(), d_meta + P, d_lens + P,
+                                         d_meta + 3ull * P, ctx->e_rev.as<uint8_t>()))
+            return r;
+        if (int r = run_end(eq.data(), et.data(), ctx->e_rev.as<const char>(), d_meta + 2ull * P,
+                            ctx->e_rev.as<const char>(), d_meta + 3ull * P, left))
+            return r;
+        if (int r = stage_add(5)) return r;  // the extension is alignment time
+        std::string text;
+        uint64_t used = 0;
+        for (uint32_t p = 0; p < P; ++p) {
+            const uint32_t r = pair_read[p];
+            score[r] = mid.sc[p] + left.sc[p] + right.sc[p];
+            q_begin[r] -= left.gi[p];
+            t_begin[r] -= left.gj[p];
+            q_end[r] += right.gi[p];
+            t_end[r] += right.gj[p];
+            if (!opt->want_cigar) continue;
+            if (!tmap::stitch_cigar(left.cig.data() + left.co[p], left.co[p + 1] - left.co[p],
+                                    mid.cig.data() + mid.co[p], mid.co[p + 1] - mid.co[p],
+                                    right.cig.data() + right.co[p], right.co[p + 1] - right.co[p], text))
+                return fail(ctx, TM_ERR_DEVICE, "--extend-ends: a malformed CIGAR piece");
+            if (used + text.size() > arena_bytes) return fail(ctx, TM_ERR_CAPACITY, "cigar arena too small");
+            std::memcpy(arena + used, text.data(), text.size());
+            cigar_off[r] = used;
+            cigar_len[r] = (uint32_t)text.size();
+            used += text.size();
+        }
+        return TM_OK;
+    };
+    if (extend_ends) {
+        Round mid;
+        rc = run(&mid);
+        if (rc == TM_OK) rc = stage(6);  // (the windows' download)
+        if (rc == TM_OK) rc = extend(mid);
+        if (rc == TM_OK) rc = stage_add(6);  // (the stitching)
+    } else if (!band_auto) {
         rc = run(nullptr);
     } else {
         // round 1 over every window, round 2 (a second plan with its own ta_device_io)
@@ -601,7 +777,7 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
     ta_plan_destroy(plan);
     ta_banded_plan_destroy(bplan);
     ta_banded_affine_plan_destroy(aplan);
-    if (rc == TM_OK) rc = stage(6);
+    if (rc == TM_OK && !extend_ends) rc = stage(6);
     return rc;
 }
 
@@ -625,7 +801,7 @@ int tm_map_files(const char* reference_path, const char* reads_path, const tm_op
 
 static int map_files_impl(const char* reference_path, const char* reads_path, const tm_options* opt,
                           const char* out_path, int device, uint32_t flags, const uint32_t* band,
-                          const int* gap_open = nullptr, bool band_auto = false);
+                          const int* gap_open = nullptr, bool band_auto = false, bool extend_ends = false);
 
 int tm_map_files_x(const char* reference_path, const char* reads_path, const tm_options* opt, const char* out_path,
                    int device, uint32_t flags) {
@@ -642,6 +818,11 @@ int tm_map_files_band_affine(const char* reference_path, const char* reads_path,
     return map_files_impl(reference_path, reads_path, opt, out_path, device, flags, &band, &gap_open);
 }
 
+int tm_map_files_band_ends(const char* reference_path, const char* reads_path, const tm_options* opt,
+                           const char* out_path, int device, uint32_t flags, uint32_t band, const int* gap_open) {
+    return map_files_impl(reference_path, reads_path, opt, out_path, device, flags, &band, gap_open, false, true);
+}
+
 int tm_map_files_band_exact(const char* reference_path, const char* reads_path, const tm_options* opt,
                             const char* out_path, int device, uint32_t flags, const int* gap_open) {
     const uint32_t none = 0;
@@ -650,8 +831,10 @@ int tm_map_files_band_exact(const char* reference_path, const char* reads_path, 
 
 static int map_files_impl(const char* reference_path, const char* reads_path, const tm_options* opt,
                           const char* out_path, int device, uint32_t flags, const uint32_t* band, const int* gap_open,
-                          bool band_auto) {
+                          bool band_auto, bool extend_ends) {
     if (!reference_path || !reads_path || !opt || !out_path || (flags & ~TM_MAP_EQX)) return TM_ERR_ARG;
+    // (before any file is read: the same rules as tm_map_batch_band_ends)
+    if (extend_ends && (!band || band_auto || opt->type != TA_GLOBAL || (flags & TM_MAP_EQX))) return TM_ERR_ARG;
     const bool eqx = (flags & TM_MAP_EQX) != 0;
     tmap::FastxFile ref, reads;
     std::string err;
@@ -698,7 +881,10 @@ static int map_files_impl(const char* reference_path, const char* reads_path, co
         for (uint32_t i = 0; i < nr; ++i) {
             off[i] = reads.records[b + i].off - base;
             len[i] = (uint32_t)reads.records[b + i].len;
-            arena_bytes += 4ull * len[i] + 2;
+            // a run takes at least 2 bytes and consumes at least one base: the window's CIGAR fits
+            // 4 len + 2; with extended ends each end's target may be `band` longer than its query
+            // (tm_ends_arena_extra: the band term is bounded whatever the band)
+            arena_bytes += 4ull * len[i] + 2 + (extend_ends ? tm_ends_arena_extra(len[i], *band) : 0);
         }
         std::vector<uint8_t> mapped(nr), fwd(nr);
         std::vector<uint32_t> qb(nr), qe(nr), tb(nr), te(nr), cl(nr);
@@ -708,7 +894,8 @@ static int map_files_impl(const char* reference_path, const char* reads_path, co
         std::vector<ta_pair_info> info(eqx ? nr : 0);
         rc = map_batch_impl(ctx, idx, nr, reads.seq.data() + base, off.data(), len.data(), &o, mapped.data(),
                             fwd.data(), qb.data(), qe.data(), tb.data(), te.data(), sc.data(), arena.data(), arena.size(),
-                            co.data(), cl.data(), flags, eqx ? info.data() : nullptr, band, gap_open, band_auto);
+                            co.data(), cl.data(), flags, eqx ? info.data() : nullptr, band, gap_open, band_auto,
+                            extend_ends);
         if (rc) {
             std::fprintf(stderr, "map: %s: %s\n", tm_status_string(rc), tm_last_error(ctx));
             break;

@@ -93,6 +93,8 @@ struct tm_context {
     tmap::DevBuf m_qoff, m_toff, m_score, m_tb, m_slots, m_cstart, m_clen, m_coff, m_cdst;
     tmap::DevBuf m_eslots, m_estart, m_elen, m_info;  // TM_MAP_EQX: the annotate pass's outputs
     tmap::DevBuf m_exact, m_need;  // band auto: the certificate of a round (ta_banded[_affine]_plan_certify)
+    // --extend-ends: one end's anchored plan (its offsets, outputs and goal cells) and the reversed left ends
+    tmap::DevBuf e_qoff, e_toff, e_score, e_tb, e_slots, e_cstart, e_clen, e_qend, e_tend, e_meta, e_rev;
     double stage_ms[tmap::kStages] = {};
     uint64_t stage_cells = 0;
     uint64_t plan_stats[5] = {};  // tm_align_plan_stats

@@ -44,6 +44,7 @@ int main(int argc, char** argv) {
     bool band_auto = false;  // --band auto: a certified band per window, the unbanded results (not in help() either)
     bool affine = false;  // --gap-open O (with --band): affine gaps, -g is the gap extend (not in help() either)
     int gap_open = 0;
+    bool extend_ends = false;  // --extend-ends (with --band N, -a global): windows extended to the read's ends (not in help())
     if (argc < 2) {
         std::fprintf(stderr, "Error: Not enough arguments\n");
         help();
@@ -83,6 +84,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(a, "-d") && more) device = std::atoi(argv[++i]);
         else if (!std::strcmp(a, "-c")) o.want_cigar = 1;
         else if (!std::strcmp(a, "--eqx")) flags |= TM_MAP_EQX;
+        else if (!std::strcmp(a, "--extend-ends")) extend_ends = true;
         else if (!std::strcmp(a, "--band") && more && !std::strcmp(argv[i + 1], "auto")) {
             ++i;
             banded = band_auto = true;
@@ -127,7 +129,20 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "Error: --gap-open requires --band (there is no unbanded affine mapper path)\n");
         return 1;
     }
-    const int r = band_auto ? tm_map_files_band_exact(f1.c_str(), f2.c_str(), &o, "-", device, flags,
+    if (extend_ends) {
+        const char* why = band_auto ? "a numeric --band, not --band auto"
+                          : !banded ? "--band N"
+                          : o.type != TA_GLOBAL ? "-a global"
+                          : (flags & TM_MAP_EQX) ? "a run without --eqx"
+                                                 : nullptr;
+        if (why) {
+            std::fprintf(stderr, "Error: --extend-ends requires %s\n", why);
+            return 1;
+        }
+    }
+    const int r = extend_ends ? tm_map_files_band_ends(f1.c_str(), f2.c_str(), &o, "-", device, flags, band,
+                                                       affine ? &gap_open : nullptr)
+                  : band_auto ? tm_map_files_band_exact(f1.c_str(), f2.c_str(), &o, "-", device, flags,
                                                       affine ? &gap_open : nullptr)
                   : affine   ? tm_map_files_band_affine(f1.c_str(), f2.c_str(), &o, "-", device, flags, band, gap_open)
                   : banded ? tm_map_files_band(f1.c_str(), f2.c_str(), &o, "-", device, flags, band)

@@ -15,4 +15,9 @@ int match_device(tm_context* ctx, uint32_t n_reads, const MinimizerOut& m, const
 int compact_segments(tm_context* ctx, uint32_t n, const char* d_src, const uint64_t* d_start, const uint32_t* d_len,
                      DevBuf& d_off, DevBuf& d_dst, DevBuf& tmp, uint64_t& total);
 
+// tm_ends.hip: n byte segments written backwards, dst[dst_off[s] + k] =
+// src[src_end[s] - 1 - k] for k < len[s] (the left ends of --extend-ends).
+int reverse_gather(tm_context* ctx, uint32_t n, const uint8_t* d_src, const uint64_t* d_src_end, const uint32_t* d_len,
+                   const uint64_t* d_dst_off, uint8_t* d_dst);
+
 }  // namespace tmap

@@ -33,7 +33,8 @@ ABI_SYMBOLS = ["tm_status_string", "tm_last_error", "tm_context_create", "tm_con
                "tm_minimize_batch", "tm_chain_batch", "tm_index_create", "tm_index_destroy", "tm_index_stats",
                "tm_map_batch", "tm_stage_times", "tm_align_plan_stats", "tm_map_files", "tm_map_batch_x",
                "tm_map_files_x", "tm_map_batch_band", "tm_map_files_band", "tm_map_batch_band_affine",
-               "tm_map_files_band_affine", "tm_map_batch_band_exact", "tm_map_files_band_exact"]
+               "tm_map_files_band_affine", "tm_map_batch_band_exact", "tm_map_files_band_exact",
+               "tm_map_batch_band_ends", "tm_map_files_band_ends", "tm_ends_arena_extra"]
 TM_MAP_EQX = 1
 
 _lib = None
@@ -89,6 +90,10 @@ def lib() -> C.CDLL:
     L.tm_map_files_band_affine.argtypes = L.tm_map_files_band.argtypes + [C.c_int]
     L.tm_map_batch_band_exact.argtypes = L.tm_map_batch_x.argtypes + [C.POINTER(C.c_int)]  # gap_open, nullable
     L.tm_map_files_band_exact.argtypes = L.tm_map_files_x.argtypes + [C.POINTER(C.c_int)]
+    L.tm_map_batch_band_ends.argtypes = L.tm_map_batch_band.argtypes + [C.POINTER(C.c_int)]  # gap_open, nullable
+    L.tm_map_files_band_ends.argtypes = L.tm_map_files_band.argtypes + [C.POINTER(C.c_int)]
+    L.tm_ends_arena_extra.restype = C.c_uint64
+    L.tm_ends_arena_extra.argtypes = [C.c_uint32, C.c_uint32]
     _lib = L
     return L
 
@@ -255,7 +260,8 @@ class Index:
         return dict(zip(["fwd_keys", "rev_keys", "fwd_positions", "rev_positions", "banned_fwd", "banned_rev"],
                         [x.value for x in v]))
 
-    def map_batch(self, reads, opt: Options, eqx: bool = False, band=None, gap_open=None) -> MapResult:
+    def map_batch(self, reads, opt: Options, eqx: bool = False, band=None, gap_open=None,
+                  extend_ends: bool = False) -> MapResult:
         """reads: sequences, or a prepared (bytes, off, len) tuple (see soa()).
         eqx: tm_map_batch_x with TM_MAP_EQX -- =/X CIGARs and the info records.
         band: None, or the band of every window (tm_map_batch_band: the banded
@@ -263,11 +269,16 @@ class Index:
         gap_open: None, or (with a band) the gap open of the banded affine
         extension (tm_map_batch_band_affine; opt.gap is the gap extend).
         band="auto": a certified band per window (tm_map_batch_band_exact) --
-        the results of band=None; with gap_open, of unbanded affine gaps."""
+        the results of band=None; with gap_open, of unbanded affine gaps.
+        extend_ends: with a numeric band, the global type and eqx=False, every
+        window is extended to the read's ends by anchored alignment and the
+        three CIGARs are stitched (tm_map_batch_band_ends)."""
         L = lib()
         if gap_open is not None and band is None:
             raise ValueError("gap_open needs a band: the mapper has no unbanded affine path")
         auto = isinstance(band, str)
+        if extend_ends and (band is None or auto or int(opt.type) != 0 or eqx):
+            raise ValueError("extend_ends needs a numeric band, the global type and eqx=False")
         if auto and band != "auto":
             raise ValueError("band: a number in [0, 2^32) or 'auto'")
         if band is not None and not auto and not 0 <= int(band) <= 0xFFFFFFFF:
@@ -278,10 +289,15 @@ class Index:
                    q_end=np.zeros(n, np.uint32), t_begin=np.zeros(n, np.uint32), t_end=np.zeros(n, np.uint32),
                    scores=np.zeros(n, np.int32), cigar_off=np.zeros(n, np.uint64), cigar_len=np.zeros(n, np.uint32))
         cap = int((4 * ln.astype(np.uint64) + 2).sum()) if n else 0
+        if extend_ends:  # (the band term is bounded whatever the band)
+            cap += sum(int(L.tm_ends_arena_extra(int(x), int(band))) for x in ln)
         arena = np.zeros(max(cap, 1), np.uint8)
         if band is not None:
             info = np.zeros(n, _align.PAIR_INFO_DTYPE) if eqx else None
-            if auto:
+            if extend_ends:
+                fn, more = L.tm_map_batch_band_ends, (int(band),
+                                                      None if gap_open is None else C.byref(C.c_int(int(gap_open))))
+            elif auto:
                 fn, more = L.tm_map_batch_band_exact, (None if gap_open is None else C.byref(C.c_int(int(gap_open))),)
             elif gap_open is None:
                 fn, more = L.tm_map_batch_band, (int(band),)
@@ -326,13 +342,23 @@ class Index:
             pass
 
 
-def map_files(reference: str, reads: str, out: str = "-", device: int = 0, band=None, gap_open=None, **opts) -> None:
+def map_files(reference: str, reads: str, out: str = "-", device: int = 0, band=None, gap_open=None,
+              extend_ends: bool = False, **opts) -> None:
     """The whole mapper on files, in process (tm_map_files; band: tm_map_files_band;
     band and gap_open: tm_map_files_band_affine, gap being the gap extend;
-    band="auto": tm_map_files_band_exact, the unbanded results)."""
+    band="auto": tm_map_files_band_exact, the unbanded results; extend_ends
+    with a numeric band and the global type: tm_map_files_band_ends)."""
     o = Options.make(**opts)
     if gap_open is not None and band is None:
         raise ValueError("gap_open needs a band: the mapper has no unbanded affine path")
+    if extend_ends:
+        if band is None or isinstance(band, str) or int(o.type) != 0:
+            raise ValueError("extend_ends needs a numeric band and the global type")
+        if not 0 <= int(band) <= 0xFFFFFFFF:
+            raise ValueError("band: must be in [0, 2^32)")
+        _check(lib().tm_map_files_band_ends(reference.encode(), reads.encode(), C.byref(o), out.encode(), device, 0,
+                                            int(band), None if gap_open is None else C.byref(C.c_int(int(gap_open)))))
+        return
     if isinstance(band, str):
         if band != "auto":
             raise ValueError("band: a number in [0, 2^32) or 'auto'")

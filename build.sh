@@ -54,12 +54,14 @@ cc "$B/ta_misc.o" "$CS/ta_kernels.hip" "$HIPCC" "${FLAGS[@]}" -DTA_TU_MISC -c "$
 cc "$B/ta_annotate.o" "$CS/ta_annotate.hip" "$HIPCC" "${FLAGS[@]}" -c "$CS/ta_annotate.hip"
 # affine-gap extension (fill + traceback kernels and its plan driver)
 cc "$B/ta_affine.o" "$CS/ta_affine.hip" "$HIPCC" "${FLAGS[@]}" -c "$CS/ta_affine.hip"
-# banded extension (band-limited fill + traceback kernels and its plan driver)
-cc "$B/ta_banded.o" "$CS/ta_banded.hip" "$HIPCC" "${FLAGS[@]}" -c "$CS/ta_banded.hip"
+# banded extension (band-limited fill + traceback kernels and its plan driver); resource usage to the build log
+cc "$B/ta_banded.o" "$CS/ta_banded.hip" "$HIPCC" "${FLAGS[@]}" -Rpass-analysis=kernel-resource-usage -c "$CS/ta_banded.hip"
 # banded affine extension; its kernels' resource usage (VGPRs, scratch) goes to the build log as remarks
 cc "$B/ta_banded_affine.o" "$CS/ta_banded_affine.hip" "$HIPCC" "${FLAGS[@]}" -Rpass-analysis=kernel-resource-usage -c "$CS/ta_banded_affine.hip"
 # exact banded alignment (the certify kernel and the two-round host batches); resource usage to the build log
 cc "$B/ta_band_exact.o" "$CS/ta_band_exact.hip" "$HIPCC" "${FLAGS[@]}" -Rpass-analysis=kernel-resource-usage -c "$CS/ta_band_exact.hip"
+# anchored (free-end) alignment: the driver over the two banded families' kAnchored instantiations
+cc "$B/ta_anchored.o" "$CS/ta_anchored.cpp" "$HIPCC" "${FLAGS[@]}" -x hip -c "$CS/ta_anchored.cpp"
 cc "$B/ta_api.o" "$CS/ta_api.hip" "$HIPCC" "${FLAGS[@]}" -c "$CS/ta_api.hip"
 cc "$B/ta_server.o" "$CS/ta_server.cpp" "$HIPCC" "${FLAGS[@]}" -x hip -c "$CS/ta_server.cpp"
 cc "$B/shim.o" "$CS/team_alignment_shim.cpp" "$HIPCC" "${FLAGS[@]}" -x c++ -c "$CS/team_alignment_shim.cpp"
@@ -70,7 +72,7 @@ cc "$B/ta_planner.o" "$CS/ta_planner.cpp" g++ -O2 -std=c++17 -fPIC -Wall -c "$CS
 cc "$B/ta_pipeline.o" "$CS/ta_pipeline.cpp" g++ -O2 -std=c++17 -fPIC -Wall -I"$(dirname "$(dirname "$HIPCC")")/include" -c "$CS/ta_pipeline.cpp"
 # mapper stages (libteam_mapper.so) and the team_mapper_amd CLI
 if [ "${TA_LIB_ONLY:-0}" != 1 ]; then
-for f in tm_minimizers tm_match tm_chain; do
+for f in tm_minimizers tm_match tm_chain tm_ends; do
   cc "$B/$f.o" "$CS/$f.hip" "$HIPCC" "${FLAGS[@]}" -c "$CS/$f.hip"
 done
 for f in tm_api tm_fastx; do
@@ -79,11 +81,11 @@ done
 cc "$B/tm_main.o" "$CS/tm_main.cpp" "$HIPCC" "${FLAGS[@]}" -x c++ -c "$CS/tm_main.cpp"
 fi
 for p in "${pids[@]}"; do wait "$p"; done
-"$HIPCC" -shared -fPIC --offload-arch=gfx950 "$B"/ta_fill_{0,1,2}{0,1}.o "$B"/ta_dual_{0,1,2}{0,1}.o "$B/ta_dual_blk.o" "$B"/ta_dual_ck_{0,1,2}.o "$B/ta_walk_ck.o" "$B"/ta_flex_{0,1,2}{0,1}.o "$B"/ta_flex_ck_{0,1,2}.o "$B/ta_misc.o" "$B/ta_annotate.o" "$B/ta_affine.o" "$B/ta_banded.o" "$B/ta_banded_affine.o" "$B/ta_band_exact.o" "$B/ta_api.o" "$B/ta_server.o" "$B/ta_planner.o" "$B/ta_pipeline.o" "$B/shim.o" \
+"$HIPCC" -shared -fPIC --offload-arch=gfx950 "$B"/ta_fill_{0,1,2}{0,1}.o "$B"/ta_dual_{0,1,2}{0,1}.o "$B/ta_dual_blk.o" "$B"/ta_dual_ck_{0,1,2}.o "$B/ta_walk_ck.o" "$B"/ta_flex_{0,1,2}{0,1}.o "$B"/ta_flex_ck_{0,1,2}.o "$B/ta_misc.o" "$B/ta_annotate.o" "$B/ta_affine.o" "$B/ta_banded.o" "$B/ta_banded_affine.o" "$B/ta_band_exact.o" "$B/ta_anchored.o" "$B/ta_api.o" "$B/ta_server.o" "$B/ta_planner.o" "$B/ta_pipeline.o" "$B/shim.o" \
   -L/opt/rocm/lib -lrocprofiler-sdk-roctx -Wl,-rpath,/opt/rocm/lib -o "$OUT"
 if [ "${TA_LIB_ONLY:-0}" = 1 ]; then echo "built $OUT"; exit 0; fi
 PKG="$ROOT/bioinfo1_amd"
-"$HIPCC" -shared -fPIC --offload-arch=gfx950 "$B"/tm_{minimizers,match,chain,api,fastx}.o -L"$PKG" -lteam_alignment -lz \
+"$HIPCC" -shared -fPIC --offload-arch=gfx950 "$B"/tm_{minimizers,match,chain,ends,api,fastx}.o -L"$PKG" -lteam_alignment -lz \
   -Wl,-rpath,'$ORIGIN' -o "$PKG/libteam_mapper.so"
 "$HIPCC" --offload-arch=gfx950 "$B/tm_main.o" -L"$PKG" -lteam_mapper -lteam_alignment -Wl,-rpath,'$ORIGIN' \
   -o "$PKG/team_mapper_amd"

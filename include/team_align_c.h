@@ -633,6 +633,92 @@ int ta_align_batch_banded_affine_exact(ta_context* ctx, uint32_t n_pairs, const 
                                        uint64_t* cigar_off, uint32_t* cigar_len, uint32_t* band_used,
                                        uint8_t* rounds);
 
+/*
+ * ---- Anchored (free-end) alignment: the path starts at the known cell (0, 0)
+ * and the score chooses where it stops -- the alignment a seed-and-extend
+ * mapper runs at the two ends of a chain.  Neither the reference nor the
+ * extensions above have a counterpart; it is a plan family of its own, reached
+ * only through the entries below, and nothing above changes behaviour (type 3
+ * stays "Unknown AlignmentType provided." everywhere else).
+ *
+ * Definition, for a pair of lengths n (query) and m (target) and its band w
+ * (tests/anchored_ref.py restates it):
+ *   The band is the banded extension's: cell (i, j) exists iff
+ *   lo <= j - i <= hi, lo = min(0, m - n) - w, hi = max(0, m - n) + w;
+ *   w >= max(n, m) holds every cell.
+ *   Boundaries are global's, where in band: H(i, 0) = i * gap, H(0, j) =
+ *   j * gap, whatever the bytes ('-' included); affine: gap_open + L *
+ *   gap_extend, 0 at (0, 0), E(i, 0) = F(0, j) = -inf.
+ *   The interior recurrence is the banded extension's global one (linear:
+ *   strict '>' in the order M, I, D, free gap steps at '-' bytes) or the
+ *   banded affine extension's global H/E/F.  No clamp.
+ *   Goal: (0, 0) with score 0, unless some in-band interior cell (i, j >= 1)
+ *   has H > 0; then the first strict row-major maximum over the in-band
+ *   interior cells.  Boundary cells other than (0, 0) are never goals.
+ *   score = H(goal) >= 0.
+ *   Walk: the global walk from the goal (gi, gj) to (0, 0) (row 0 emits I x j,
+ *   column 0 D x i; affine: the three-state walk from H-state); reversal, RLE
+ *   and "1\0" for the empty op string are the reference's.  The CIGAR consumes
+ *   exactly gi query and gj target bytes.
+ *   Outputs per pair: score, query_end = gi, target_end = gj, CIGAR.  The
+ *   target_begin array of ta_device_io is written 0.
+ *   Degenerate pairs (n == 0 or m == 0): goal (0, 0), score 0, "1\0".
+ * With a full band and gi, gj > 0, score and CIGAR are those of the global
+ * alignment of query[0, gi) against target[0, gj), and no pair of prefixes has
+ * a higher global score.  With gap_open == 0 the affine kernels give the linear
+ * kernels' results at every band.  A banded score is never above the full-band
+ * score.
+ * Range: the banded families' rule ((max qlen + max tlen + 2) * max(|match|,
+ * |mismatch|, |gap_open| + |gap_extend|) < 2^26), else TA_ERR_RANGE.
+ * Certification (ta_*_plan_certify, the *_exact batches) does not cover this
+ * mode.
+ */
+typedef struct ta_anchored_plan ta_anchored_plan;
+
+#define TA_ANCHORED_AFFINE_KERNELS 1u /* run the affine kernels even at gap_open == 0 (same results) */
+
+/* As ta_banded_affine_plan_create without `type`.  gap_open == 0 runs the
+ * linear kernels (2-bit codes, gap = gap_extend) unless flags holds
+ * TA_ANCHORED_AFFINE_KERNELS; any other gap_open the affine kernels.  Other
+ * flag bits: TA_ERR_ARG. */
+int ta_anchored_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* query_len_host,
+                            const uint32_t* target_len_host, const uint32_t* band_host, int match, int mismatch,
+                            int gap_open, int gap_extend, int want_cigar, uint64_t workspace_budget,
+                            uint32_t flags, ta_anchored_plan** out);
+void ta_anchored_plan_destroy(ta_anchored_plan* plan);
+uint64_t ta_anchored_plan_cigar_slots_bytes(const ta_anchored_plan* plan);
+uint64_t ta_anchored_plan_workspace_bytes(const ta_anchored_plan* plan);
+uint32_t ta_anchored_plan_chunks(const ta_anchored_plan* plan);
+int ta_anchored_plan_pair_chunks(const ta_anchored_plan* plan, uint32_t* chunk_of_pair);
+/* As ta_banded_plan_band_cells / _swept_cells. */
+uint64_t ta_anchored_plan_band_cells(const ta_anchored_plan* plan);
+uint64_t ta_anchored_plan_swept_cells(const ta_anchored_plan* plan);
+/* Enqueue the whole batch / one chunk's fill / one chunk's traceback on hip_stream. */
+int ta_anchored_plan_execute(ta_anchored_plan* plan, const ta_device_io* io, void* hip_stream);
+int ta_anchored_plan_execute_fill(ta_anchored_plan* plan, const ta_device_io* io, void* hip_stream, uint32_t chunk);
+int ta_anchored_plan_execute_traceback(ta_anchored_plan* plan, const ta_device_io* io, void* hip_stream,
+                                       uint32_t chunk);
+/* As ta_plan_check (these kernels have no failure to report: TA_OK). */
+int ta_anchored_plan_check(ta_anchored_plan* plan);
+/* As ta_plan_annotate: begins 0 / 0, ends gi / gj, n_free = 0; the counts and
+ * the =/X CIGAR are the path's. */
+int ta_anchored_plan_annotate(ta_anchored_plan* plan, const ta_device_io* io, const ta_annotate_io* out,
+                              void* hip_stream);
+/* After an execution (or its fills; want_cigar == 0 plans too), on the same
+ * stream: the goal cells into query_end_dev[P] and target_end_dev[P].
+ * Asynchronous. */
+int ta_anchored_plan_ends(ta_anchored_plan* plan, uint32_t* query_end_dev, uint32_t* target_end_dev,
+                          void* hip_stream);
+
+/* Host-memory batch: ta_align_batch_banded_affine without `type`; the goal
+ * cells (either may be NULL) in place of target_begin. */
+int ta_align_batch_anchored(ta_context* ctx, uint32_t n_pairs, const char* query_bytes, const uint64_t* query_off,
+                            const uint32_t* query_len, const char* target_bytes, const uint64_t* target_off,
+                            const uint32_t* target_len, const uint32_t* band, int match, int mismatch,
+                            int gap_open, int gap_extend, int want_cigar, int32_t* score, uint32_t* query_end,
+                            uint32_t* target_end, char* cigar_arena, uint64_t cigar_arena_bytes,
+                            uint64_t* cigar_off, uint32_t* cigar_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,44 @@ int tm_map_batch_band_exact(tm_context* ctx, const tm_index* idx, uint32_t n_rea
                             uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags, ta_pair_info* info,
                             const int* gap_open);
 
+/* tm_map_batch_band (gap_open NULL) or tm_map_batch_band_affine (*gap_open)
+ * with every chain's window extended to the read's ends (team_mapper_amd
+ * --extend-ends).  The window [qb..qe] x [tb..te] on the chain's strand S (of
+ * length L) is aligned as before; then, with anchored alignment
+ * (ta_anchored_plan_*, team_align_c.h) at the same scoring and band w,
+ *   right end: the nr = len - 1 - qe bases after the window against
+ *     S[te+1 .. te+1+mr), mr = min(L - 1 - te, nr + w);
+ *   left end: the reverse of the nl = qb bases before the window against the
+ *     reverse of S[tb-ml .. tb), ml = min(tb, nl + w) (a gather kernel writes
+ *     the reversed bytes; the left ends run as a plan of their own).
+ * An end with no query or no target bases contributes nothing.  With the goal
+ * cells (gi, gj) of the two ends: q_begin = qb - gi_left, q_end = qe + gi_right,
+ * t_begin = tb - gj_left, t_end = te + gj_right; score = the sum of the three
+ * scores (with affine gaps a gap that crosses a junction pays its open twice);
+ * the CIGAR = the left CIGAR's runs in reverse order, the window's, the right
+ * one's, adjacent runs of one op merged ("1\0" pieces contribute nothing),
+ * stitched on the host (csrc/tm_stitch.h).  The CIGAR arena: beside the
+ * 4 * len + 2 bytes of the window's own text a read needs at most
+ * tm_ends_arena_extra(len, band) more (below).  Without want_cigar the scores and coordinates are the
+ * same (score-only fills plus ta_anchored_plan_ends).
+ * Requires opt->type == TA_GLOBAL and flags without TM_MAP_EQX (the annotate
+ * records are not stitched): otherwise TM_ERR_ARG.  The extension counts in
+ * stage [5] of tm_stage_times; the plan stats add the two end plans' chunks. */
+/* Arena bytes a read of `len` bases needs beyond 4 * len + 2 when its ends are
+ * extended at `band`: 4 * min(band, 3 * len + 6) + 4.  A run of count c takes
+ * at most 2 c bytes, and an end of nq query bases consumes at most nq + band
+ * target bases: 4 nq + 2 band per end.  Independently of the band, the runs
+ * that consume query bases take at most 2 nq bytes and the insert runs number
+ * at most nq + 1 of at most 11 bytes each: 13 nq + 11 per end, which
+ * 4 nq + 2 (3 len + 6) covers.  So any band in [0, 2^32) is cheap to ask for. */
+uint64_t tm_ends_arena_extra(uint32_t len, uint32_t band);
+int tm_map_batch_band_ends(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
+                           const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
+                           uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end,
+                           int32_t* score, char* cigar_arena, uint64_t cigar_arena_bytes, uint64_t* cigar_off,
+                           uint32_t* cigar_len, uint32_t flags, ta_pair_info* info, uint32_t band,
+                           const int* gap_open);
+
 /* Wall time (ms) of the last tm_map_batch on this context, per stage:
  * [0] read upload, [1] minimizers, [2] seed matching, [3] FindLIS chaining,
  * [4] windows + alignment plan (host), [5] alignment (fill + traceback),
@@ -205,6 +243,12 @@ int tm_map_files_band_affine(const char* reference_path, const char* reads_path,
  * output is tm_map_files_x's byte for byte; with --gap-open O, unbanded-exact affine mapping. */
 int tm_map_files_band_exact(const char* reference_path, const char* reads_path, const tm_options* opt,
                             const char* out_path, int device, uint32_t flags, const int* gap_open);
+
+/* tm_map_files_band (gap_open NULL) or tm_map_files_band_affine through tm_map_batch_band_ends
+ * (team_mapper_amd --band N --extend-ends): full-read alignments with natural soft clipping.  The PAF
+ * columns follow from the extended coordinates by the same rules. */
+int tm_map_files_band_ends(const char* reference_path, const char* reads_path, const tm_options* opt,
+                           const char* out_path, int device, uint32_t flags, uint32_t band, const int* gap_open);
 
 #ifdef __cplusplus
 }
