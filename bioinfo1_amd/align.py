@@ -201,6 +201,11 @@ def lib() -> C.CDLL:
     L.ta_anchored_plan_check.argtypes = [C.c_void_p]
     L.ta_anchored_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ta_anchored_plan_ends.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    # z-drop on anchored alignment
+    L.ta_anchored_plan_create_zdrop.argtypes = (L.ta_anchored_plan_create.argtypes[:-1]
+                                                + [C.c_int32, C.POINTER(C.c_void_p)])
+    L.ta_anchored_plan_swept_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ta_align_batch_anchored_zdrop.argtypes = L.ta_align_batch_anchored.argtypes + [C.c_int32, u32p]
     # the annotate post-pass (info records, =/X CIGARs)
     L.ta_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ta_affine_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -256,6 +261,10 @@ ABI_SYMBOLS += BAND_EXACT_ABI_SYMBOLS
 # Anchored (free-end) alignment's symbols (checked by tests/test_anchored_ref.py).
 ANCHORED_ABI_SYMBOLS = [s.replace("banded", "anchored") for s in BANDED_ABI_SYMBOLS] + ["ta_anchored_plan_ends"]
 ABI_SYMBOLS += ANCHORED_ABI_SYMBOLS
+# Z-drop on anchored alignment (checked by tests/test_anchored_zdrop_ref.py).
+ANCHORED_ZDROP_ABI_SYMBOLS = ["ta_anchored_plan_create_zdrop", "ta_anchored_plan_swept_steps",
+                              "ta_align_batch_anchored_zdrop"]
+ABI_SYMBOLS += ANCHORED_ZDROP_ABI_SYMBOLS
 TA_ANCHORED_AFFINE_KERNELS = 1  # ta_anchored_plan_create flag: the affine kernels even at gap_open == 0
 # The drop-in C++ entry point (team_alignment.hpp), g++/libstdc++ cxx11 mangling.
 TEAM_ALIGN_SYMBOL = ("_ZN4team5AlignEPKcjS1_jNS_13AlignmentTypeEiiiPNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEEPj")
@@ -294,6 +303,15 @@ def _band_array(band, n_pairs: int) -> np.ndarray:
     return np.ascontiguousarray(b.astype(np.uint32))
 
 
+def _check_zdrop(zdrop):
+    """None (off) or an int in [0, INT32_MAX]."""
+    if zdrop is None:
+        return None
+    if isinstance(zdrop, bool) or not isinstance(zdrop, (int, np.integer)) or not 0 <= int(zdrop) <= 0x7FFFFFFF:
+        raise ValueError(f"zdrop: an int in [0, 2^31) or None, not {zdrop!r}")
+    return int(zdrop)
+
+
 @dataclass
 class BatchResult:
     scores: np.ndarray  # int32 [P]
@@ -305,6 +323,7 @@ class BatchResult:
     rounds: np.ndarray | None = None  # uint8 [P], the exact banded entries: 1 or 2
     query_ends: np.ndarray | None = None  # uint32 [P], the anchored entries: the goal cell's row
     target_ends: np.ndarray | None = None  # uint32 [P], ... and its column
+    swept_steps: np.ndarray | None = None  # uint32 [P], the anchored entries with zdrop: the fill steps executed
 
     def cigar(self, p: int) -> bytes | None:
         if self.arena is None:
@@ -395,13 +414,18 @@ class Aligner:
                            band=None if band_start is None else _band_array(band_start, batch.n_pairs))
 
     def align_batch_anchored(self, batch, match: int, mismatch: int, gap: int, band, gap_open: int = 0,
-                             want_cigar: bool = True) -> BatchResult:
+                             want_cigar: bool = True, zdrop=None) -> BatchResult:
         """Anchored (free-end) alignment (ta_align_batch_anchored): every path
         starts at (0, 0) and ends at the best in-band interior cell, or stays
         at (0, 0) with score 0 when none is positive.  band: an int or one
         per pair.  gap_open == 0: linear gaps; else affine with gap_extend =
         gap.  The result carries query_ends / target_ends (the goal cells);
-        target_begins is all 0."""
+        target_begins is all 0.  zdrop=Z (an int >= 0): the sweep of a pair
+        stops once a 64-step segment's best has fallen more than Z below the
+        best so far (ta_align_batch_anchored_zdrop; a scoring with negative
+        drift, e.g. 2/-4/-4, is what makes a dead end fall), and the result
+        carries swept_steps.  zdrop=None: off."""
+        z = _check_zdrop(zdrop)
         L = lib()
         P = batch.n_pairs
         bd = _band_array(band, P)
@@ -417,16 +441,19 @@ class Aligner:
             clen = np.zeros(P, np.uint32)
         qb = batch.qbytes if batch.qbytes.size else np.zeros(1, np.uint8)
         tbb = batch.tbytes if batch.tbytes.size else np.zeros(1, np.uint8)
-        r = L.ta_align_batch_anchored(
+        steps = None if z is None else np.zeros(P, np.uint32)
+        tail = () if z is None else (z, _p(steps, C.c_uint32))
+        r = (L.ta_align_batch_anchored if z is None else L.ta_align_batch_anchored_zdrop)(
             self._h, P, qb.ctypes.data, _p(batch.qoff, C.c_uint64), _p(batch.qlen, C.c_uint32), tbb.ctypes.data,
             _p(batch.toff, C.c_uint64), _p(batch.tlen, C.c_uint32),
             _p(bd if bd.size else np.zeros(1, np.uint32), C.c_uint32), match, mismatch, gap_open, gap,
             int(bool(want_cigar)), _p(sc, C.c_int32), _p(qe, C.c_uint32), _p(te, C.c_uint32),
             arena.ctypes.data if want_cigar else None, cap, _p(coff, C.c_uint64) if want_cigar else None,
-            _p(clen, C.c_uint32) if want_cigar else None)
+            _p(clen, C.c_uint32) if want_cigar else None, *tail)
         if r != TA_OK:
             _raise(r, self._h)
-        return BatchResult(sc, np.zeros(P, np.uint32), coff, clen, arena, query_ends=qe, target_ends=te)
+        return BatchResult(sc, np.zeros(P, np.uint32), coff, clen, arena, query_ends=qe, target_ends=te,
+                           swept_steps=steps)
 
     def _batch(self, batch, type, scoring, want_cigar, affine, band=None, exact=False) -> BatchResult:
         L = lib()
@@ -519,12 +546,13 @@ def align_banded_affine(query: bytes, target: bytes, type, match: int, mismatch:
 
 
 def align_anchored(query: bytes, target: bytes, match: int, mismatch: int, gap: int, band: int, gap_open: int = 0,
-                   want_cigar: bool = True):
-    """Anchored alignment for one pair -> (score, cigar bytes or None, query_end, target_end)."""
+                   want_cigar: bool = True, zdrop=None):
+    """Anchored alignment for one pair -> (score, cigar bytes or None, query_end, target_end).
+    zdrop: as Aligner.align_batch_anchored."""
     from .synth import from_pairs
 
     res = default_aligner().align_batch_anchored(from_pairs([(bytes(query), bytes(target))]), match, mismatch, gap,
-                                                 band, gap_open, want_cigar)
+                                                 band, gap_open, want_cigar, zdrop=zdrop)
     return int(res.scores[0]), res.cigar(0), int(res.query_ends[0]), int(res.target_ends[0])
 
 
@@ -679,7 +707,7 @@ class DevicePlan:
 
     def __init__(self, aligner: Aligner, batch, type, match, mismatch, gap, want_cigar=True, device=None,
                  workspace_budget: int = 0, gap_open=None, flags: int = 0, inputs=None, records=None, band=None,
-                 _banded_affine: bool = False, _anchored: bool = False):
+                 _banded_affine: bool = False, _anchored: bool = False, _zdrop=None):
         """gap_open=None: team::Align's linear gap.  gap_open=o: the affine-gap
         extension (ta_affine_plan_*) with gap_extend = gap.  flags: TA_PLAN_*
         kernel selection (tests / measurements; same results).  inputs: the
@@ -704,6 +732,7 @@ class DevicePlan:
         self.affine = gap_open is not None
         self.banded = band is not None
         self.anchored = _anchored
+        self.zdrop = _check_zdrop(_zdrop) if _anchored else None
         family = ("ta_anchored_plan_" if _anchored else "ta_banded_affine_plan_" if self.affine and self.banded else
                   "ta_affine_plan_" if self.affine else "ta_banded_plan_" if self.banded else "ta_plan_")
         self._fn = lambda name: getattr(L, name.replace("ta_plan_", family))
@@ -713,9 +742,10 @@ class DevicePlan:
         if self.banded:
             self.band = _band_array(band, self.P)
             extra = (_p(self.band if self.band.size else np.zeros(1, np.uint32), C.c_uint32),)
-        r = self._fn("ta_plan_create")(aligner.handle, self.P, _p(batch.qlen, C.c_uint32),
-                                       _p(batch.tlen, C.c_uint32), *extra, *t, *scoring, int(self.want_cigar),
-                                       workspace_budget, flags, C.byref(h))
+        create, ztail = ("ta_plan_create", ()) if self.zdrop is None else ("ta_plan_create_zdrop", (self.zdrop,))
+        r = self._fn(create)(aligner.handle, self.P, _p(batch.qlen, C.c_uint32),
+                             _p(batch.tlen, C.c_uint32), *extra, *t, *scoring, int(self.want_cigar),
+                             workspace_budget, flags, *ztail, C.byref(h))
         if r != TA_OK:
             _raise(r, aligner.handle)
         self._h = h
@@ -765,17 +795,38 @@ class DevicePlan:
 
     @classmethod
     def anchored(cls, aligner: Aligner, batch, match, mismatch, gap, band, gap_open: int = 0, want_cigar=True,
-                 workspace_budget: int = 0, flags: int = 0, device=None, inputs=None, records=None):
+                 workspace_budget: int = 0, flags: int = 0, device=None, inputs=None, records=None, zdrop=None):
         """A plan of anchored (free-end) alignment (ta_anchored_plan_*): every
         path starts at (0, 0) and ends at the best in-band interior cell.
         band: an int, or one per pair.  gap_open == 0: the linear kernels
         (flags=TA_ANCHORED_AFFINE_KERNELS: the affine ones); else affine gaps
         with gap_extend = gap.  run / results / annotate / pair_chunks /
         band_cells / swept_cells as on a banded plan; ends() returns the goal
-        cells; certify() raises."""
+        cells; certify() raises.  zdrop=Z (an int >= 0): a z-drop plan
+        (ta_anchored_plan_create_zdrop) -- sized as without it; swept_steps()
+        returns the fill steps each pair executed."""
         return cls(aligner, batch, None, match, mismatch, gap, want_cigar, device, workspace_budget,
                    gap_open=int(gap_open), flags=flags, inputs=inputs, records=records, band=band,
-                   _banded_affine=True, _anchored=True)
+                   _banded_affine=True, _anchored=True, _zdrop=zdrop)
+
+    def swept_steps_async(self):
+        """Z-drop plans: enqueue the copy of the last run()'s (or fills') per-pair
+        step counts on the current stream (ta_anchored_plan_swept_steps) -> an
+        int32 device tensor, allocated on first use."""
+        if not self.anchored or self.zdrop is None:
+            raise AttributeError("swept_steps: not a z-drop plan")
+        if getattr(self, "swept", None) is None:
+            self.swept = self.torch.zeros(max(self.P, 1), dtype=self.torch.int32, device=self.dev)
+        r = lib().ta_anchored_plan_swept_steps(self._h, self.swept.data_ptr(), self._stream())
+        if r != TA_OK:
+            _raise(r, self._ctx)
+        return self.swept
+
+    def swept_steps(self):
+        """Z-drop plans, after run() or the fills: uint32 numpy array [P]."""
+        s = self.swept_steps_async()
+        self.torch.cuda.synchronize(self.dev)
+        return s[:self.P].cpu().numpy().view(np.uint32)
 
     def ends_async(self):
         """Anchored plans: enqueue the copy of the last run()'s goal cells on the

@@ -25,6 +25,14 @@ extern "C" {
 int ta_anchored_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
                             const uint32_t* band, int match, int mismatch, int gap_open, int gap_extend,
                             int want_cigar, uint64_t budget, uint32_t flags, ta_anchored_plan** out) {
+    return ta_anchored_plan_create_zdrop(ctx, n_pairs, qlen, tlen, band, match, mismatch, gap_open, gap_extend,
+                                         want_cigar, budget, flags, -1, out);
+}
+
+int ta_anchored_plan_create_zdrop(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
+                                  const uint32_t* band, int match, int mismatch, int gap_open, int gap_extend,
+                                  int want_cigar, uint64_t budget, uint32_t flags, int32_t zdrop,
+                                  ta_anchored_plan** out) {
     if (!out) return TA_ERR_ARG;
     *out = nullptr;
     if (!ctx) return TA_ERR_ARG;
@@ -34,9 +42,9 @@ int ta_anchored_plan_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* q
     pl->ctx = ctx;
     const bool affine = gap_open != 0 || (flags & TA_ANCHORED_AFFINE_KERNELS);
     const int r = affine ? ta_host::anchored_affine_create(ctx, n_pairs, qlen, tlen, band, match, mismatch, gap_open,
-                                                           gap_extend, want_cigar, budget, &pl->aff)
+                                                           gap_extend, want_cigar, budget, zdrop, &pl->aff)
                          : ta_host::anchored_linear_create(ctx, n_pairs, qlen, tlen, band, match, mismatch,
-                                                           gap_extend, want_cigar, budget, &pl->lin);
+                                                           gap_extend, want_cigar, budget, zdrop, &pl->lin);
     if (r != TA_OK) {
         delete pl;
         return r;
@@ -98,18 +106,34 @@ int ta_anchored_plan_ends(ta_anchored_plan* pl, uint32_t* query_end_dev, uint32_
                            ta_host::anchored_affine_ends(pl->aff, query_end_dev, target_end_dev, stream));
 }
 
+int ta_anchored_plan_swept_steps(ta_anchored_plan* pl, uint32_t* steps_dev, void* stream) {
+    return TA_ANCHORED_FWD(pl, TA_ERR_ARG, ta_host::anchored_linear_swept_steps(pl->lin, steps_dev, stream),
+                           ta_host::anchored_affine_swept_steps(pl->aff, steps_dev, stream));
+}
+
 int ta_align_batch_anchored(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
                             const uint32_t* qlen, const char* tbytes, const uint64_t* toff, const uint32_t* tlen,
                             const uint32_t* band, int match, int mismatch, int gap_open, int gap_extend,
                             int want_cigar, int32_t* score, uint32_t* query_end, uint32_t* target_end, char* arena,
                             uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len) {
+    return ta_align_batch_anchored_zdrop(ctx, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, band, match, mismatch,
+                                         gap_open, gap_extend, want_cigar, score, query_end, target_end, arena,
+                                         arena_bytes, cigar_off, cigar_len, -1, nullptr);
+}
+
+int ta_align_batch_anchored_zdrop(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
+                                  const uint32_t* qlen, const char* tbytes, const uint64_t* toff,
+                                  const uint32_t* tlen, const uint32_t* band, int match, int mismatch, int gap_open,
+                                  int gap_extend, int want_cigar, int32_t* score, uint32_t* query_end,
+                                  uint32_t* target_end, char* arena, uint64_t arena_bytes, uint64_t* cigar_off,
+                                  uint32_t* cigar_len, int32_t zdrop, uint32_t* swept_steps) {
     if (gap_open != 0)
         return ta_host::anchored_affine_batch(ctx, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, band, match, mismatch,
                                               gap_open, gap_extend, want_cigar, score, query_end, target_end, arena,
-                                              arena_bytes, cigar_off, cigar_len);
+                                              arena_bytes, cigar_off, cigar_len, zdrop, swept_steps);
     return ta_host::anchored_linear_batch(ctx, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, band, match, mismatch,
                                           gap_extend, want_cigar, score, query_end, target_end, arena, arena_bytes,
-                                          cigar_off, cigar_len);
+                                          cigar_off, cigar_len, zdrop, swept_steps);
 }
 
 }  // extern "C"

@@ -82,14 +82,18 @@ struct BandAffArgs {
     const uint64_t* slot_off;
     uint64_t* cigar_start;
     uint32_t* cigar_len;
+    int zdrop;        // z-drop plans (the DROP kernels): Z >= 0
+    uint32_t* swept;  // ... per pair, the fill steps executed
 };
 
 // One pass = rows row_base+1 .. row_base+nrows against the columns c0 .. c1.
 //   QDASH  some query row of this pass is '-' (its vertical gap steps are free)
-template <int MODE, bool CIGAR, bool QDASH>
+//   DROP   z-drop (kAnchored only), as ta_banded.hip band_pass
+template <int MODE, bool CIGAR, bool QDASH, bool DROP = false>
 __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uint8_t* Q, const uint8_t* T, uint32_t n,
                                                  uint32_t m, uint32_t w, uint32_t pass, bool last_pass, uint2* prow,
-                                                 int2* B, int lane) {
+                                                 int2* B, int lane, DropIO* drop = nullptr) {
+    static_assert(!DROP || MODE == kAnchored, "z-drop is anchored alignment's");
     constexpr int R = kRows;
     constexpr bool ARGMAX = MODE == kLocal || MODE == kAnchored;  // the goal is the best interior cell
     const int O = a.open, X = a.extend, OX = wadd(a.open, a.extend);
@@ -157,6 +161,7 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
     uint32_t bestj = 0;
     int rowbest = kFloor;
     uint32_t rowbest_j = 0;
+    int segkey = INT_MIN;  // DROP: the lane's best stepkey of the current segment
 
     // the previous pass's bottom row, 64 columns c0 + 64 k + lane per chunk; what it did
     // not sweep (beyond its c1) is out of band in that row, and so is never read
@@ -241,7 +246,7 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
                     f = inb ? f : kSent;
                 }
                 // (kSent << 4 would wrap: an out-of-band cell keys as h = -1.  Anchored: no clamp, so in
-                // every step -- the padding rows below row n can fall below -2^26 -- each h <= 0 keys
+                // every step -- the padding rows below row n can fall below -2^26 -- each h < 0 keys
                 // as -1; only h > 0 can move the goal)
                 if constexpr (ARGMAX) {
                     const int hk = (MASKED || MODE == kAnchored) ? max(h, -1) : h;
@@ -258,6 +263,7 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
                     bestkey = stepkey;
                     bestj = (uint32_t)j;
                 }
+                if constexpr (DROP) segkey = max(segkey, stepkey);
             }
             if constexpr (MODE == kSemi) {
                 if (last_pass) {  // row n is register nv-1 of lane nl-1
@@ -281,9 +287,30 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
     const uint32_t u0 = (uint32_t)min(max(t_in, 0), (int)steps);
     const uint32_t u1 = (uint32_t)min(max(t_out, (int)u0), (int)steps);
     uint32_t t = 0;
-    for (; t < u0; ++t) step(t, std::true_type{});
-    for (; t < u1; ++t) step(t, std::false_type{});
-    for (; t < steps; ++t) step(t, std::true_type{});
+    if constexpr (!DROP) {
+        for (; t < u0; ++t) step(t, std::true_type{});
+        for (; t < u1; ++t) step(t, std::false_type{});
+        for (; t < steps; ++t) step(t, std::true_type{});
+    } else {
+        // The same three ranges, cut at the segment boundaries (the unmasked body stays unmasked).
+        while (t < steps) {
+            const uint32_t tend = min(steps, t + (uint32_t)kDropSteps);  // (t is a multiple of kDropSteps here)
+            for (const uint32_t e1 = min(u0, tend); t < e1; ++t) step(t, std::true_type{});
+            for (const uint32_t e2 = min(u1, tend); t < e2; ++t) step(t, std::false_type{});
+            for (; t < tend; ++t) step(t, std::true_type{});
+            // S against B' = max(B, S), the best with this segment included: the same answer
+            // as against B (ta_banded.hip band_pass).  Wave-uniform: a scalar branch.
+            const bool used = (uint32_t)lane < nl;
+            const int S = max(__builtin_amdgcn_readfirstlane(wave_max(used ? (segkey >> 4) : INT_MIN)), -1);
+            const int Bp = max(drop->best, __builtin_amdgcn_readfirstlane(wave_max(used ? (bestkey >> 4) : INT_MIN)));
+            segkey = INT_MIN;
+            if (Bp >= drop->z && S < Bp - drop->z) {  // (Bp < 2^26, Z <= INT32_MAX: no overflow)
+                drop->dropped = true;
+                break;
+            }
+        }
+        drop->steps += t;
+    }
 
     PassOut o{kFloor, 0, 0, kFloor, 0, 0};
     if constexpr (ARGMAX) {
@@ -324,7 +351,7 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
 }
 
 // (the anchored score-only fill is held to the local one's waves per SIMD; 0: no bound)
-template <int MODE, bool CIGAR>
+template <int MODE, bool CIGAR, bool DROP = false>
 __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 3 : 0) void banded_affine_fill_kernel(BandAffArgs a) {
     const int lane = threadIdx.x & 63;
     const uint32_t widx = wave_id();
@@ -351,6 +378,7 @@ __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 3 : 0) void
             a.target_begin[p] = tb;
             a.goal_i[p] = gi;
             a.goal_j[p] = gj;
+            if constexpr (DROP) a.swept[p] = 0;
         }
         return;
     }
@@ -366,19 +394,25 @@ __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 3 : 0) void
     int best_h = ((MODE == kSemi && (int)m <= hi) || MODE == kAnchored) ? 0 : kFloor;
     uint32_t best_i = 0, best_j = (MODE == kSemi) ? m : 0;
     int corner = 0;
+    DropIO drop{0, a.zdrop, 0u, false};
     for (uint32_t pass = 0; pass < passes; ++pass) {
         const bool last_pass = pass + 1 == passes;
         bool dash = false;
         const uint32_t row0 = pass * kPassRows + (uint32_t)lane * kRows;
 #pragma unroll
         for (int r = 0; r < kRows; ++r) dash |= (row0 + r < n) && Q[row0 + r] == '-';
-        const PassOut o = __ballot(dash)
-                              ? band_aff_pass<MODE, CIGAR, true>(a, Q, T, n, m, w, pass, last_pass, prow, B, lane)
-                              : band_aff_pass<MODE, CIGAR, false>(a, Q, T, n, m, w, pass, last_pass, prow, B, lane);
+        if constexpr (DROP) drop.best = best_h;  // the best of the passes above
+        const PassOut o =
+            __ballot(dash)
+                ? band_aff_pass<MODE, CIGAR, true, DROP>(a, Q, T, n, m, w, pass, last_pass, prow, B, lane, &drop)
+                : band_aff_pass<MODE, CIGAR, false, DROP>(a, Q, T, n, m, w, pass, last_pass, prow, B, lane, &drop);
         if (MODE != kGlobal && o.h > best_h) {  // strict: the upper pass wins ties
             best_h = o.h;
             best_i = o.i;
             best_j = o.j;
+        }
+        if constexpr (DROP) {
+            if (drop.dropped) break;  // the passes below do not exist (wave-uniform; nobody waits on this wave)
         }
         if (MODE == kSemi && last_pass) {  // row n after column m (:271-278): (n, 0) first, cost 0
             if (-(int)n >= lo && 0 > best_h) {
@@ -401,6 +435,7 @@ __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 3 : 0) void
         a.target_begin[p] = (MODE == kLocal) ? best_j + 1 : 0;  // :117-121 / :197-199 / :283-285
         a.goal_i[p] = (MODE == kGlobal) ? n : best_i;
         a.goal_j[p] = (MODE == kGlobal) ? m : best_j;
+        if constexpr (DROP) a.swept[p] = drop.steps;
     }
 }
 
@@ -435,6 +470,12 @@ inline dim3 band_aff_grid(uint32_t waves) { return dim3((waves + kWavesPerBlock 
 hipError_t launch_banded_affine_fill(int mode, bool cigar, const BandAffArgs& a, hipStream_t s) {
     if (a.count == 0) return hipSuccess;
     const dim3 g = band_aff_grid(a.count), b(kBlock);
+    if (a.zdrop >= 0) {  // z-drop plans: anchored only
+        if (mode != kAnchored || !a.swept) return hipErrorInvalidValue;
+        if (cigar) hipLaunchKernelGGL((banded_affine_fill_kernel<kAnchored, true, true>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((banded_affine_fill_kernel<kAnchored, false, true>), g, b, 0, s, a);
+        return hipGetLastError();
+    }
 #define TA_BAND_AFF_FILL(M)                                                                    \
     case M:                                                                                    \
         if (cigar) hipLaunchKernelGGL((banded_affine_fill_kernel<M, true>), g, b, 0, s, a);    \
@@ -533,6 +574,8 @@ int ta_banded_affine_plan::exec_chunk(ta_banded_affine_plan* pl, const ta_device
     a.slot_off = pl->d_slot_off;
     a.cigar_start = io->cigar_start;
     a.cigar_len = io->cigar_len;
+    a.zdrop = h.zdrop;
+    a.swept = pl->d_swept;
     if (fill) {
         roctxRangePushA("ta banded affine fill");
         TA_HIP(ctx, ta::launch_banded_affine_fill(h.type, h.want_cigar, a, s));
@@ -634,7 +677,7 @@ namespace ta_host {
 
 int anchored_affine_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
                            const uint32_t* band, int match, int mismatch, int gap_open, int gap_extend, int want_cigar,
-                           uint64_t budget, ta_banded_affine_plan** out) {
+                           uint64_t budget, int32_t zdrop, ta_banded_affine_plan** out) {
     if (!out) return TA_ERR_ARG;
     *out = nullptr;
     if (int r = band_aff_check_args(ctx, n_pairs, qlen, tlen, band, TA_GLOBAL, match, mismatch, gap_open, gap_extend))
@@ -643,7 +686,7 @@ int anchored_affine_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* ql
     auto* pl = new ta_banded_affine_plan();
     pl->ctx = ctx;
     ta::build_band_affine_plan(pl->h, n_pairs, qlen, tlen, band, ta::kAnchored, match, mismatch, gap_open, gap_extend,
-                               want_cigar != 0, budget ? budget : default_budget(ctx));
+                               want_cigar != 0, budget ? budget : default_budget(ctx), zdrop);
     return plan_create_block(pl, "ta_anchored_plan_create: ", out);
 }
 
@@ -651,11 +694,16 @@ int anchored_affine_ends(ta_banded_affine_plan* pl, uint32_t* query_end_dev, uin
     return plan_ends(pl, query_end_dev, target_end_dev, stream);
 }
 
+int anchored_affine_swept_steps(ta_banded_affine_plan* pl, uint32_t* steps_dev, void* stream) {
+    return plan_swept_steps(pl, steps_dev, stream);
+}
+
 int anchored_affine_batch(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
                           const uint32_t* qlen, const char* tbytes, const uint64_t* toff, const uint32_t* tlen,
                           const uint32_t* band, int match, int mismatch, int gap_open, int gap_extend, int want_cigar,
                           int32_t* score, uint32_t* query_end, uint32_t* target_end, char* arena,
-                          uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len) {
+                          uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len, int32_t zdrop,
+                          uint32_t* swept_steps) {
     uint64_t qend = 0, tend = 0;
     if (int r = check_host_batch(ctx, TA_GLOBAL, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, want_cigar, arena,
                                  cigar_off, cigar_len, &qend, &tend))
@@ -673,11 +721,11 @@ int anchored_affine_batch(ta_context* ctx, uint32_t n_pairs, const char* qb, con
     // everything in one chunk while the codes take at most 1 GiB (no device query per call)
     const uint64_t budget = need <= (1ull << 30) ? std::max<uint64_t>(need, 1) : default_budget(ctx);
     ta::build_band_affine_plan(pl.h, n_pairs, qlen, tlen, band, ta::kAnchored, match, mismatch, gap_open, gap_extend,
-                               want_cigar != 0, budget);
+                               want_cigar != 0, budget, zdrop);
     if (int r = host_batch(ctx, pl, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
                            nullptr, arena, arena_bytes, cigar_off, cigar_len))
         return r;
-    return batch_ends(ctx, pl, query_end, target_end);
+    return batch_ends(ctx, pl, query_end, target_end, swept_steps);
 }
 
 }  // namespace ta_host

@@ -391,5 +391,13 @@ struct PassOut {
     int corner;      // global, last pass: H[n][m]
 };
 
+// Z-drop state of one pair across the passes of a banded anchored fill (all wave-uniform).
+struct DropIO {
+    int best;        // in: the best H of the passes above (>= 0)
+    int z;           // in: Z >= 0
+    uint32_t steps;  // in / out: the fill steps executed so far
+    bool dropped;    // out: the pair dropped in this pass
+};
+
 }  // namespace
 }  // namespace ta

@@ -167,6 +167,38 @@ TA_HD inline uint64_t band_pass_offset(uint32_t n, uint32_t m, uint32_t w, uint3
 TA_HD inline uint64_t band_ptr_dwords(uint32_t n, uint32_t m, uint32_t w) {
     return (n == 0 || m == 0) ? 0 : band_pass_offset(n, m, w, n_passes(n));
 }
+// ---- Z-drop on anchored alignment (the rule is DEFINED in include/team_align_c.h
+// and restated in tests/anchored_zdrop_ref.py).  The drop is tied to the fill's
+// sweep order: pass p executes band_drop_steps steps (its columns plus the skew
+// of the stripes in use -- not the 63 of the code layout), the in-band interior
+// cell (i, j) is computed at step band_drop_tau of its pass, and the rule is
+// applied once per segment of kDropSteps steps.
+constexpr int kDropSteps = 64;
+TA_HD inline uint32_t band_drop_steps(uint32_t n, uint32_t m, uint32_t w, uint32_t pass) {
+    const uint32_t row_base = pass * kPassRows;
+    const uint32_t nrows = n - row_base < (uint32_t)kPassRows ? n - row_base : (uint32_t)kPassRows;
+    const uint32_t nl = (nrows + kRows - 1) / kRows;
+    return band_c1(n, m, w, pass) - band_c0(n, m, w, pass) + 1 + nl - 1;
+}
+TA_HD inline uint32_t band_drop_segments(uint32_t n, uint32_t m, uint32_t w, uint32_t pass) {
+    return (band_drop_steps(n, m, w, pass) + kDropSteps - 1) / kDropSteps;
+}
+// 1 <= i <= n, 1 <= j <= m, (i, j) in band
+TA_HD inline uint32_t band_drop_tau(uint32_t n, uint32_t m, uint32_t w, uint32_t i, uint32_t j) {
+    return j - band_c0(n, m, w, (i - 1) / kPassRows) + ((i - 1) % kPassRows) / kRows;
+}
+// Steps a pair executes when it drops in segment s of pass p; p == n_passes(n): when nothing drops.
+TA_HD inline uint64_t band_drop_swept_steps(uint32_t n, uint32_t m, uint32_t w, uint32_t pass, uint32_t seg) {
+    if (n == 0 || m == 0) return 0;
+    uint64_t steps = 0;
+    for (uint32_t p = 0; p < pass; ++p) steps += band_drop_steps(n, m, w, p);
+    if (pass < n_passes(n)) {
+        const uint32_t sp = band_drop_steps(n, m, w, pass), cut = (uint32_t)kDropSteps * (seg + 1);
+        steps += cut < sp ? cut : sp;
+    }
+    return steps;
+}
+
 // In-band interior cells (1 <= i <= n, 1 <= j <= m) and the cells the passes sweep.
 TA_HD inline uint64_t band_cells(uint32_t n, uint32_t m, uint32_t w) {
     if (n == 0 || m == 0) return 0;

@@ -121,6 +121,7 @@ struct BandArrays {
     uint32_t *d_qlen = nullptr, *d_tlen = nullptr, *d_band = nullptr, *d_order = nullptr;
     uint32_t *d_goal_i = nullptr, *d_goal_j = nullptr;
     uint64_t *d_ptr_off = nullptr, *d_bnd_off = nullptr, *d_slot_off = nullptr;
+    uint32_t* d_swept = nullptr;  // z-drop plans: per pair, the fill steps executed
 };
 
 template <class H, class V>
@@ -135,6 +136,7 @@ void band_block_arrays(const H& h, BandArrays& d, V& v) {
     v.device_only();
     v.scratch(d.d_goal_i, 4ull * h.n_pairs);
     v.scratch(d.d_goal_j, 4ull * h.n_pairs);
+    v.scratch(d.d_swept, h.zdrop >= 0 ? 4ull * h.n_pairs : 0);  // (0 bytes: the block is the zdrop < 0 plan's)
 }
 template <class V>
 void block_arrays(const BandPlan& h, BandArrays& d, V& v) {

@@ -197,13 +197,33 @@ int plan_ends(PL* pl, uint32_t* query_end_dev, uint32_t* target_end_dev, void* s
     return TA_OK;
 }
 
-// ... and after a host batch (its stream drained, ctx->mu still held): the goal cells to host arrays.
+// Z-drop plans (an anchored plan with zdrop >= 0): enqueue the copy of the last
+// execution's per-pair step counts, after it (or its fills) on the same stream.
 template <class PL>
-int batch_ends(ta_context* ctx, const PL& pl, uint32_t* query_end, uint32_t* target_end) {
+int plan_swept_steps(PL* pl, uint32_t* steps_dev, void* stream) {
+    if (!pl) return TA_ERR_ARG;
+    ta_context* ctx = pl->ctx;
+    if (pl->h.zdrop < 0) return fail(ctx, TA_ERR_ARG, "swept_steps: not a z-drop plan");
+    if (!pl->h.n_pairs) return TA_OK;
+    if (!steps_dev) return fail(ctx, TA_ERR_ARG, "swept_steps: null output");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    TA_HIP(ctx, hipSetDevice(ctx->device));
+    TA_HIP(ctx, hipMemcpyAsync(steps_dev, pl->d_swept, 4ull * pl->h.n_pairs, hipMemcpyDeviceToDevice,
+                               (hipStream_t)stream));
+    return TA_OK;
+}
+
+// ... and after a host batch (its stream drained, ctx->mu still held): the goal cells to host arrays.
+// swept_steps: z-drop plans only (else it must be null).
+template <class PL>
+int batch_ends(ta_context* ctx, const PL& pl, uint32_t* query_end, uint32_t* target_end,
+               uint32_t* swept_steps = nullptr) {
     const size_t bytes = 4ull * pl.h.n_pairs;
     hipStream_t s = ctx->stream;
     if (query_end) TA_HIP(ctx, hipMemcpyAsync(query_end, pl.d_goal_i, bytes, hipMemcpyDeviceToHost, s));
     if (target_end) TA_HIP(ctx, hipMemcpyAsync(target_end, pl.d_goal_j, bytes, hipMemcpyDeviceToHost, s));
+    if (swept_steps && pl.h.zdrop >= 0)
+        TA_HIP(ctx, hipMemcpyAsync(swept_steps, pl.d_swept, bytes, hipMemcpyDeviceToHost, s));
     TA_HIP(ctx, hipStreamSynchronize(s));
     return TA_OK;
 }

@@ -665,10 +665,11 @@ Assembly assemble_band(P& pl, uint32_t n_pairs, const uint32_t* qlen, const uint
 }  // namespace
 
 void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
-                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget) {
+                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget, int32_t zdrop) {
     pl = BandPlan{};
     init_plan(pl, n_pairs, qlen, tlen, type, match, mismatch, want_cigar);
     pl.gap = gap;
+    pl.zdrop = (type == kAnchored && zdrop >= 0) ? zdrop : -1;
     const Assembly as = assemble_band(pl, n_pairs, qlen, tlen, band, budget / 4);
     for (const Cut& c : as.cuts) pl.chunks.push_back({{c.begin, c.count}, c.codes, c.bnd});
     pl.ws_ptr_dwords = as.ws_codes;
@@ -677,11 +678,12 @@ void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const
 
 void build_band_affine_plan(BandAffinePlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
                             const uint32_t* band, int type, int match, int mismatch, int gap_open, int gap_extend,
-                            bool want_cigar, uint64_t budget) {
+                            bool want_cigar, uint64_t budget, int32_t zdrop) {
     pl = BandAffinePlan{};
     init_plan(pl, n_pairs, qlen, tlen, type, match, mismatch, want_cigar);
     pl.open = gap_open;
     pl.extend = gap_extend;
+    pl.zdrop = (type == kAnchored && zdrop >= 0) ? zdrop : -1;
     const Assembly as = assemble_band(pl, n_pairs, qlen, tlen, band, budget / 8);
     for (const Cut& c : as.cuts) pl.chunks.push_back({{c.begin, c.count}, c.codes, c.bnd});
     pl.ws_ptr_entries = as.ws_codes;

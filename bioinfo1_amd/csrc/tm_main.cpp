@@ -45,6 +45,7 @@ int main(int argc, char** argv) {
     bool affine = false;  // --gap-open O (with --band): affine gaps, -g is the gap extend (not in help() either)
     int gap_open = 0;
     bool extend_ends = false;  // --extend-ends (with --band N, -a global): windows extended to the read's ends (not in help())
+    int zdrop = -1;  // --zdrop Z (with --extend-ends): both end extensions stop once the end has died (not in help())
     if (argc < 2) {
         std::fprintf(stderr, "Error: Not enough arguments\n");
         help();
@@ -111,6 +112,16 @@ int main(int argc, char** argv) {
             affine = true;
             gap_open = (int)v;
         }
+        else if (!std::strcmp(a, "--zdrop") && more) {
+            char* end = nullptr;
+            errno = 0;
+            const long v = std::strtol(argv[++i], &end, 10);
+            if (end == argv[i] || *end || errno || argv[i][0] == '-' || argv[i][0] == '+' || v < 0 || v > INT_MAX) {
+                std::fprintf(stderr, "Error: --zdrop expects a decimal integer in [0, 2^31)\n");
+                return 1;
+            }
+            zdrop = (int)v;
+        }
         else if (!std::strcmp(a, "-s")) std::fprintf(stderr, "note: -s (statistics) is not part of this build\n");
         else if (f1.empty()) f1 = a;
         else if (f2.empty()) f2 = a;
@@ -140,8 +151,15 @@ int main(int argc, char** argv) {
             return 1;
         }
     }
-    const int r = extend_ends ? tm_map_files_band_ends(f1.c_str(), f2.c_str(), &o, "-", device, flags, band,
-                                                       affine ? &gap_open : nullptr)
+    if (zdrop >= 0 && !extend_ends) {
+        std::fprintf(stderr, "Error: --zdrop requires --extend-ends\n");
+        return 1;
+    }
+    if (zdrop >= 0 && band > 32)  // (the band caveat: the rule follows the fill's step order)
+        std::fprintf(stderr, "warning: --zdrop with --band above 32 can clip a live end longer than 1024 bases at "
+                             "row 1024; use --band 32 or less, or a large Z\n");
+    const int r = extend_ends ? tm_map_files_band_ends_zdrop(f1.c_str(), f2.c_str(), &o, "-", device, flags, band,
+                                                             affine ? &gap_open : nullptr, zdrop)
                   : band_auto ? tm_map_files_band_exact(f1.c_str(), f2.c_str(), &o, "-", device, flags,
                                                       affine ? &gap_open : nullptr)
                   : affine   ? tm_map_files_band_affine(f1.c_str(), f2.c_str(), &o, "-", device, flags, band, gap_open)

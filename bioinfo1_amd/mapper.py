@@ -34,7 +34,8 @@ ABI_SYMBOLS = ["tm_status_string", "tm_last_error", "tm_context_create", "tm_con
                "tm_map_batch", "tm_stage_times", "tm_align_plan_stats", "tm_map_files", "tm_map_batch_x",
                "tm_map_files_x", "tm_map_batch_band", "tm_map_files_band", "tm_map_batch_band_affine",
                "tm_map_files_band_affine", "tm_map_batch_band_exact", "tm_map_files_band_exact",
-               "tm_map_batch_band_ends", "tm_map_files_band_ends", "tm_ends_arena_extra"]
+               "tm_map_batch_band_ends", "tm_map_files_band_ends", "tm_ends_arena_extra",
+               "tm_map_batch_band_ends_zdrop", "tm_map_files_band_ends_zdrop"]
 TM_MAP_EQX = 1
 
 _lib = None
@@ -92,6 +93,8 @@ def lib() -> C.CDLL:
     L.tm_map_files_band_exact.argtypes = L.tm_map_files_x.argtypes + [C.POINTER(C.c_int)]
     L.tm_map_batch_band_ends.argtypes = L.tm_map_batch_band.argtypes + [C.POINTER(C.c_int)]  # gap_open, nullable
     L.tm_map_files_band_ends.argtypes = L.tm_map_files_band.argtypes + [C.POINTER(C.c_int)]
+    L.tm_map_batch_band_ends_zdrop.argtypes = L.tm_map_batch_band_ends.argtypes + [C.c_int32]
+    L.tm_map_files_band_ends_zdrop.argtypes = L.tm_map_files_band_ends.argtypes + [C.c_int32]
     L.tm_ends_arena_extra.restype = C.c_uint64
     L.tm_ends_arena_extra.argtypes = [C.c_uint32, C.c_uint32]
     _lib = L
@@ -261,7 +264,7 @@ class Index:
                         [x.value for x in v]))
 
     def map_batch(self, reads, opt: Options, eqx: bool = False, band=None, gap_open=None,
-                  extend_ends: bool = False) -> MapResult:
+                  extend_ends: bool = False, zdrop=None) -> MapResult:
         """reads: sequences, or a prepared (bytes, off, len) tuple (see soa()).
         eqx: tm_map_batch_x with TM_MAP_EQX -- =/X CIGARs and the info records.
         band: None, or the band of every window (tm_map_batch_band: the banded
@@ -272,8 +275,12 @@ class Index:
         the results of band=None; with gap_open, of unbanded affine gaps.
         extend_ends: with a numeric band, the global type and eqx=False, every
         window is extended to the read's ends by anchored alignment and the
-        three CIGARs are stitched (tm_map_batch_band_ends)."""
+        three CIGARs are stitched (tm_map_batch_band_ends).
+        zdrop: with extend_ends, Z of the z-drop rule for both ends
+        (tm_map_batch_band_ends_zdrop): an end that has died is clipped there
+        and its sweep stops."""
         L = lib()
+        zdrop = _check_zdrop(zdrop, extend_ends)
         if gap_open is not None and band is None:
             raise ValueError("gap_open needs a band: the mapper has no unbanded affine path")
         auto = isinstance(band, str)
@@ -297,6 +304,8 @@ class Index:
             if extend_ends:
                 fn, more = L.tm_map_batch_band_ends, (int(band),
                                                       None if gap_open is None else C.byref(C.c_int(int(gap_open))))
+                if zdrop is not None:
+                    fn, more = L.tm_map_batch_band_ends_zdrop, more + (zdrop,)
             elif auto:
                 fn, more = L.tm_map_batch_band_exact, (None if gap_open is None else C.byref(C.c_int(int(gap_open))),)
             elif gap_open is None:
@@ -342,13 +351,24 @@ class Index:
             pass
 
 
+def _check_zdrop(zdrop, extend_ends):
+    """None, or (only with extend_ends) an int in [0, 2^31)."""
+    if zdrop is None:
+        return None
+    if not extend_ends:
+        raise ValueError("zdrop needs extend_ends")
+    return _align._check_zdrop(zdrop)
+
+
 def map_files(reference: str, reads: str, out: str = "-", device: int = 0, band=None, gap_open=None,
-              extend_ends: bool = False, **opts) -> None:
+              extend_ends: bool = False, zdrop=None, **opts) -> None:
     """The whole mapper on files, in process (tm_map_files; band: tm_map_files_band;
     band and gap_open: tm_map_files_band_affine, gap being the gap extend;
     band="auto": tm_map_files_band_exact, the unbanded results; extend_ends
-    with a numeric band and the global type: tm_map_files_band_ends)."""
+    with a numeric band and the global type: tm_map_files_band_ends; zdrop
+    with extend_ends: tm_map_files_band_ends_zdrop)."""
     o = Options.make(**opts)
+    zdrop = _check_zdrop(zdrop, extend_ends)
     if gap_open is not None and band is None:
         raise ValueError("gap_open needs a band: the mapper has no unbanded affine path")
     if extend_ends:
@@ -356,8 +376,13 @@ def map_files(reference: str, reads: str, out: str = "-", device: int = 0, band=
             raise ValueError("extend_ends needs a numeric band and the global type")
         if not 0 <= int(band) <= 0xFFFFFFFF:
             raise ValueError("band: must be in [0, 2^32)")
-        _check(lib().tm_map_files_band_ends(reference.encode(), reads.encode(), C.byref(o), out.encode(), device, 0,
-                                            int(band), None if gap_open is None else C.byref(C.c_int(int(gap_open)))))
+        go = None if gap_open is None else C.byref(C.c_int(int(gap_open)))
+        if zdrop is None:
+            _check(lib().tm_map_files_band_ends(reference.encode(), reads.encode(), C.byref(o), out.encode(), device,
+                                                0, int(band), go))
+        else:
+            _check(lib().tm_map_files_band_ends_zdrop(reference.encode(), reads.encode(), C.byref(o), out.encode(),
+                                                      device, 0, int(band), go, zdrop))
         return
     if isinstance(band, str):
         if band != "auto":

@@ -719,6 +719,57 @@ int ta_align_batch_anchored(ta_context* ctx, uint32_t n_pairs, const char* query
                             uint32_t* target_end, char* cigar_arena, uint64_t cigar_arena_bytes,
                             uint64_t* cigar_off, uint32_t* cigar_len);
 
+/*
+ * ---- Z-drop on anchored alignment: stop the sweep once the end has died.
+ * Cell values are anchored alignment's: same band, boundaries, recurrence, tie
+ * order and '-' bytes, in both gap families; nothing is pruned.  The drop only
+ * decides which cells EXIST for the goal scan, and -- like ksw2's -- it is tied
+ * to the order in which the fill sweeps them (tests/anchored_zdrop_ref.py
+ * restates it; the geometry is ta_layout.h band_drop_*):
+ *   Step index.  An in-band interior cell (i, j) lies in pass p = (i-1) div 1024
+ *   and is computed at step tau(i, j) = j - c0(p) + ((i-1) mod 1024) div 16 of
+ *   it, c0(p) = max(1, 1024 p + 1 + lo) the pass's first swept column.  Its
+ *   segment is (p, tau div 64).  Pass p has ceil(steps_p / 64) segments,
+ *   steps_p = c1(p) - c0(p) + 1 + nl_p - 1, c1(p) = min(m, 1024 p + rows_p + hi),
+ *   nl_p = ceil(rows_p / 16), rows_p the pass's query rows.
+ *   Scan.  Segments in order (pass, then segment), B = 0 at the start:
+ *     S = the maximum of -1 and every H of the segment's in-band interior cells
+ *     with i <= n (an empty segment: -1);
+ *     if B >= Z and S < B - Z the pair DROPS: this segment's cells still exist,
+ *     every later segment's cells, and those of later passes, do not;
+ *     otherwise B = max(B, S).
+ *   Goal: (0, 0) with score 0 unless an existing cell has H > 0, else the first
+ *   strict row-major maximum over the existing cells.
+ *   Walk, CIGAR, "1\0", degenerate pairs and the range rule are unchanged.
+ *   Z: 0 <= zdrop <= INT32_MAX.  zdrop < 0 is off: the plan, the kernels and
+ *   the results are ta_anchored_plan_create's.
+ *   swept_steps, per pair: the fill steps the pair executed -- the whole passes
+ *   before the drop plus min(64 (s + 1), steps_p) in the dropping pass (p, s);
+ *   the sum of steps_p when nothing drops; 0 for a degenerate pair.
+ * A drop needs a scoring with negative drift (2/-4/-4, say): at 1/-1/-1 random
+ * DNA drifts upward inside a band and nothing drops.
+ * Planning (codes, slots, chunks, boundary rows) is sized as without z-drop: a
+ * drop only leaves workspace unused.  _annotate, _ends, _check and _pair_chunks
+ * work unchanged on a z-drop plan; certification does not cover the mode.
+ */
+int ta_anchored_plan_create_zdrop(ta_context* ctx, uint32_t n_pairs, const uint32_t* query_len_host,
+                                  const uint32_t* target_len_host, const uint32_t* band_host, int match,
+                                  int mismatch, int gap_open, int gap_extend, int want_cigar,
+                                  uint64_t workspace_budget, uint32_t flags, int32_t zdrop, ta_anchored_plan** out);
+/* Z-drop plans (else TA_ERR_ARG), after an execution (or its fills; want_cigar
+ * == 0 plans too), on the same stream: swept_steps into steps_dev[P].
+ * Asynchronous. */
+int ta_anchored_plan_swept_steps(ta_anchored_plan* plan, uint32_t* steps_dev, void* hip_stream);
+/* ta_align_batch_anchored with Z (zdrop < 0: exactly that call) and, where
+ * zdrop >= 0, the per-pair swept_steps (may be NULL). */
+int ta_align_batch_anchored_zdrop(ta_context* ctx, uint32_t n_pairs, const char* query_bytes,
+                                  const uint64_t* query_off, const uint32_t* query_len, const char* target_bytes,
+                                  const uint64_t* target_off, const uint32_t* target_len, const uint32_t* band,
+                                  int match, int mismatch, int gap_open, int gap_extend, int want_cigar,
+                                  int32_t* score, uint32_t* query_end, uint32_t* target_end, char* cigar_arena,
+                                  uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
+                                  int32_t zdrop, uint32_t* swept_steps);
+
 #ifdef __cplusplus
 }
 #endif

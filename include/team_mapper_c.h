@@ -207,6 +207,17 @@ int tm_map_batch_band_ends(tm_context* ctx, const tm_index* idx, uint32_t n_read
                            int32_t* score, char* cigar_arena, uint64_t cigar_arena_bytes, uint64_t* cigar_off,
                            uint32_t* cigar_len, uint32_t flags, ta_pair_info* info, uint32_t band,
                            const int* gap_open);
+/* ... with z-drop (team_mapper_amd --extend-ends --zdrop Z): both end plans
+ * are z-drop plans at Z = zdrop (ta_anchored_plan_create_zdrop, team_align_c.h),
+ * so an end whose alignment has died is clipped there and its sweep stops.  The
+ * stitching, the arena rule and the stage accounting are unchanged.  zdrop < 0:
+ * tm_map_batch_band_ends exactly. */
+int tm_map_batch_band_ends_zdrop(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
+                                 const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
+                                 uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin,
+                                 uint32_t* t_end, int32_t* score, char* cigar_arena, uint64_t cigar_arena_bytes,
+                                 uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags, ta_pair_info* info,
+                                 uint32_t band, const int* gap_open, int32_t zdrop);
 
 /* Wall time (ms) of the last tm_map_batch on this context, per stage:
  * [0] read upload, [1] minimizers, [2] seed matching, [3] FindLIS chaining,
@@ -249,6 +260,10 @@ int tm_map_files_band_exact(const char* reference_path, const char* reads_path, 
  * columns follow from the extended coordinates by the same rules. */
 int tm_map_files_band_ends(const char* reference_path, const char* reads_path, const tm_options* opt,
                            const char* out_path, int device, uint32_t flags, uint32_t band, const int* gap_open);
+/* ... through tm_map_batch_band_ends_zdrop (team_mapper_amd --band N --extend-ends --zdrop Z). */
+int tm_map_files_band_ends_zdrop(const char* reference_path, const char* reads_path, const tm_options* opt,
+                                 const char* out_path, int device, uint32_t flags, uint32_t band,
+                                 const int* gap_open, int32_t zdrop);
 
 #ifdef __cplusplus
 }
