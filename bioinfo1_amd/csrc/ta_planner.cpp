@@ -54,10 +54,17 @@ bool flex_ck_fits(int mode, uint32_t n, uint32_t m, int ma, int mi, int gap) {
            (mode != kLocal || flex_local_fits(n, m, ma, mi, gap));
 }
 
+// The semi-global packed fills (ta_dual.hip, ta_affine.hip) keep the column of row n's
+// best in a 16-bit half beside the value.  The value bounds below cap m for most
+// scorings, but with match == gap (affine: match == extend) the bias -ma*j + gap*(j - i)
+// does not depend on j and they admit any m: the cap is stated on its own.
+constexpr uint32_t kSemiColumnMax = 65535;
+
 // Bounds of the biased 16-bit values of ta_dual.hip (S and every candidate),
 // with a margin; pairs that do not fit run in the int32 kernel.
 bool fits_int16(int mode, uint32_t n, uint32_t m, int ma, int mi, int gap) {
     if (n == 0 || m == 0) return false;
+    if (mode == kSemi && m > kSemiColumnMax) return false;
     const long long N = n, M = m;
     const long long mag = std::max({1LL, std::llabs(ma), std::llabs(mi), std::llabs(gap)});
     const long long hmax = std::min(N, M) * std::max({0LL, (long long)ma, (long long)mi}) + (N + M) * std::max(0LL, (long long)gap);
@@ -107,6 +114,7 @@ bool fits_int16(int mode, uint32_t n, uint32_t m, int ma, int mi, int gap) {
 // covered too.
 bool affine_fits_int16(int mode, uint32_t n, uint32_t m, int ma, int mi, int open, int ext) {
     if (mode == kLocal || n == 0 || m == 0) return false;
+    if (mode == kSemi && m > kSemiColumnMax) return false;  // (row n's column is a 16-bit half)
     const long long N = n, N1 = N + 16, M = m, O = open, X = ext;
     const long long hs = std::max({0LL, (long long)ma, (long long)mi});
     const long long gp = std::max(0LL, O) + std::max(0LL, X);

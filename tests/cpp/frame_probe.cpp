@@ -7,6 +7,12 @@
 //   mode ma mi gap cap         the largest square L <= cap each predicate admits (0: none)
 //   m mode ma mi gap n cap     the largest m <= cap each predicate admits beside n rows
 //   p mode ma mi gap cigar flags n m [n m ...]   what build_plan makes of these pairs
+// and of the affine family (affine_fits_int16, build_affine_plan):
+//   a mode ma mi open ext n m      the predicate and the pass count at an n x m pair
+//   e mode ma mi open ext cap      the largest square L <= cap it admits (0: none)
+//   w mode ma mi open ext n cap    the widest m <= cap it admits beside n rows
+//   t mode ma mi open ext m cap    the tallest n <= cap it admits beside m columns
+//   q mode ma mi open ext cigar flags n m [n m ...]   what build_affine_plan makes of these pairs
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -40,13 +46,49 @@ const Pred kPreds[] = {
     {"max3_eq", [](int, int ma, int mi, int g, uint32_t n, uint32_t m) { return ta::local_max3_offset(n, m, ma, mi, g, true) >= 0; }},
 };
 
+// the affine family's lines (v: the numbers after the kind letter); false: malformed
+bool affine_line(char kind, const std::vector<long>& v) {
+    if (v.size() < 6) return false;
+    const int mode = (int)v[0], ma = (int)v[1], mi = (int)v[2], O = (int)v[3], X = (int)v[4];
+    auto fits = [&](long n, long m) { return ta::affine_fits_int16(mode, (uint32_t)n, (uint32_t)m, ma, mi, O, X); };
+    if (kind == 'a' && v.size() == 7) {
+        std::printf("aff_at fits=%d passes=%u\n", (int)fits(v[5], v[6]), ta::n_passes((uint32_t)v[5]));
+    } else if (kind == 'e' && v.size() == 6) {
+        long L = v[5];
+        while (L > 0 && !fits(L, L)) --L;
+        std::printf("aff_square edge=%ld\n", L);
+    } else if (kind == 'w' && v.size() == 7) {
+        long m = v[6];
+        while (m > 0 && !fits(v[5], m)) --m;
+        std::printf("aff_wide edge=%ld\n", m);
+    } else if (kind == 't' && v.size() == 7) {
+        long n = v[6];
+        while (n > 0 && !fits(n, v[5])) --n;
+        std::printf("aff_tall edge=%ld passes=%u\n", n, ta::n_passes((uint32_t)n));
+    } else if (kind == 'q' && v.size() >= 9 && v.size() % 2 == 1) {
+        std::vector<uint32_t> ql, tl;
+        for (size_t k = 7; k < v.size(); k += 2) {
+            ql.push_back((uint32_t)v[k]);
+            tl.push_back((uint32_t)v[k + 1]);
+        }
+        ta::AffinePlan pl;
+        ta::build_affine_plan(pl, (uint32_t)ql.size(), ql.data(), tl.data(), mode, ma, mi, O, X, v[5] != 0, 1ull << 30,
+                              (uint32_t)v[6]);
+        std::printf("aff_plan couples=%zu singles=%zu dual_pairs=%zu chunks=%zu\n", pl.duals.size() / 2, pl.singles.size(),
+                    pl.duals.size(), pl.chunks.size());
+    } else {
+        return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 int main() {
     std::string line;
     while (std::getline(std::cin, line)) {
         if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
-        const char kind = line[0] == 'm' || line[0] == 'p' ? line[0] : ' ';
+        const char kind = std::string("mpaewtq").find(line[0]) != std::string::npos ? line[0] : ' ';
         std::istringstream in(kind == ' ' ? line : line.substr(1));
         std::vector<long> v;
         for (long x; in >> x;) v.push_back(x);
@@ -55,6 +97,13 @@ int main() {
             return 2;
         }
         const int mode = (int)v[0], ma = (int)v[1], mi = (int)v[2], gap = (int)v[3];
+        if (std::string("aewtq").find(kind) != std::string::npos) {
+            if (!affine_line(kind, v)) {
+                std::fprintf(stderr, "frame_probe: cannot read line: %s\n", line.c_str());
+                return 2;
+            }
+            continue;
+        }
         if (kind == 'p' && v.size() >= 8 && v.size() % 2 == 0) {
             std::vector<uint32_t> ql, tl;
             for (size_t k = 6; k < v.size(); k += 2) {
