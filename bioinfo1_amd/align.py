@@ -206,6 +206,10 @@ def lib() -> C.CDLL:
                                                 + [C.c_int32, C.POINTER(C.c_void_p)])
     L.ta_anchored_plan_swept_steps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.ta_align_batch_anchored_zdrop.argtypes = L.ta_align_batch_anchored.argtypes + [C.c_int32, u32p]
+    # ... with the rule chosen (TA_ZDROP_SEGMENT / TA_ZDROP_STRIPE)
+    L.ta_anchored_plan_create_zdrop_rule.argtypes = (L.ta_anchored_plan_create.argtypes[:-1]
+                                                     + [C.c_int32, C.c_int, C.POINTER(C.c_void_p)])
+    L.ta_align_batch_anchored_zdrop_rule.argtypes = L.ta_align_batch_anchored.argtypes + [C.c_int32, C.c_int, u32p]
     # the annotate post-pass (info records, =/X CIGARs)
     L.ta_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ta_affine_plan_annotate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -265,6 +269,10 @@ ABI_SYMBOLS += ANCHORED_ABI_SYMBOLS
 ANCHORED_ZDROP_ABI_SYMBOLS = ["ta_anchored_plan_create_zdrop", "ta_anchored_plan_swept_steps",
                               "ta_align_batch_anchored_zdrop"]
 ABI_SYMBOLS += ANCHORED_ZDROP_ABI_SYMBOLS
+# The row-stripe z-drop rule's entries (checked by tests/test_anchored_zdrop_stripe_ref.py).
+ANCHORED_ZDROP_RULE_ABI_SYMBOLS = ["ta_anchored_plan_create_zdrop_rule", "ta_align_batch_anchored_zdrop_rule"]
+ABI_SYMBOLS += ANCHORED_ZDROP_RULE_ABI_SYMBOLS
+TA_ZDROP_SEGMENT, TA_ZDROP_STRIPE = 0, 1  # the z-drop rules of include/team_align_c.h
 TA_ANCHORED_AFFINE_KERNELS = 1  # ta_anchored_plan_create flag: the affine kernels even at gap_open == 0
 # The drop-in C++ entry point (team_alignment.hpp), g++/libstdc++ cxx11 mangling.
 TEAM_ALIGN_SYMBOL = ("_ZN4team5AlignEPKcjS1_jNS_13AlignmentTypeEiiiPNSt7__cxx1112basic_stringIcSt11char_traitsIcESaIcEEEPj")
@@ -310,6 +318,13 @@ def _check_zdrop(zdrop):
     if isinstance(zdrop, bool) or not isinstance(zdrop, (int, np.integer)) or not 0 <= int(zdrop) <= 0x7FFFFFFF:
         raise ValueError(f"zdrop: an int in [0, 2^31) or None, not {zdrop!r}")
     return int(zdrop)
+
+
+def _check_zdrop_rule(rule) -> int:
+    """"segment" (the rule on the fill's 64-step segments) or "stripe" (on 16-row stripes) -> TA_ZDROP_*."""
+    if not isinstance(rule, str) or rule not in ("segment", "stripe"):
+        raise ValueError(f'zdrop_rule: "segment" or "stripe", not {rule!r}')
+    return TA_ZDROP_STRIPE if rule == "stripe" else TA_ZDROP_SEGMENT
 
 
 @dataclass
@@ -414,7 +429,7 @@ class Aligner:
                            band=None if band_start is None else _band_array(band_start, batch.n_pairs))
 
     def align_batch_anchored(self, batch, match: int, mismatch: int, gap: int, band, gap_open: int = 0,
-                             want_cigar: bool = True, zdrop=None) -> BatchResult:
+                             want_cigar: bool = True, zdrop=None, zdrop_rule: str = "segment") -> BatchResult:
         """Anchored (free-end) alignment (ta_align_batch_anchored): every path
         starts at (0, 0) and ends at the best in-band interior cell, or stays
         at (0, 0) with score 0 when none is positive.  band: an int or one
@@ -424,8 +439,12 @@ class Aligner:
         stops once a 64-step segment's best has fallen more than Z below the
         best so far (ta_align_batch_anchored_zdrop; a scoring with negative
         drift, e.g. 2/-4/-4, is what makes a dead end fall), and the result
-        carries swept_steps.  zdrop=None: off."""
+        carries swept_steps.  zdrop=None: off.  zdrop_rule="stripe": the drop
+        is decided on 16-row stripes instead (ta_align_batch_anchored_zdrop_rule,
+        TA_ZDROP_STRIPE) -- the rule to use above band 32, where the segment
+        rule can clip a live end longer than 1,024 bases at a pass boundary."""
         z = _check_zdrop(zdrop)
+        rule = _check_zdrop_rule(zdrop_rule)
         L = lib()
         P = batch.n_pairs
         bd = _band_array(band, P)
@@ -442,8 +461,10 @@ class Aligner:
         qb = batch.qbytes if batch.qbytes.size else np.zeros(1, np.uint8)
         tbb = batch.tbytes if batch.tbytes.size else np.zeros(1, np.uint8)
         steps = None if z is None else np.zeros(P, np.uint32)
-        tail = () if z is None else (z, _p(steps, C.c_uint32))
-        r = (L.ta_align_batch_anchored if z is None else L.ta_align_batch_anchored_zdrop)(
+        tail = () if z is None else (z, _p(steps, C.c_uint32)) if rule == TA_ZDROP_SEGMENT else (
+            z, rule, _p(steps, C.c_uint32))
+        r = (L.ta_align_batch_anchored if z is None else L.ta_align_batch_anchored_zdrop if rule == TA_ZDROP_SEGMENT
+             else L.ta_align_batch_anchored_zdrop_rule)(
             self._h, P, qb.ctypes.data, _p(batch.qoff, C.c_uint64), _p(batch.qlen, C.c_uint32), tbb.ctypes.data,
             _p(batch.toff, C.c_uint64), _p(batch.tlen, C.c_uint32),
             _p(bd if bd.size else np.zeros(1, np.uint32), C.c_uint32), match, mismatch, gap_open, gap,
@@ -546,13 +567,14 @@ def align_banded_affine(query: bytes, target: bytes, type, match: int, mismatch:
 
 
 def align_anchored(query: bytes, target: bytes, match: int, mismatch: int, gap: int, band: int, gap_open: int = 0,
-                   want_cigar: bool = True, zdrop=None):
+                   want_cigar: bool = True, zdrop=None, zdrop_rule: str = "segment"):
     """Anchored alignment for one pair -> (score, cigar bytes or None, query_end, target_end).
-    zdrop: as Aligner.align_batch_anchored."""
+    zdrop, zdrop_rule: as Aligner.align_batch_anchored."""
     from .synth import from_pairs
 
     res = default_aligner().align_batch_anchored(from_pairs([(bytes(query), bytes(target))]), match, mismatch, gap,
-                                                 band, gap_open, want_cigar, zdrop=zdrop)
+                                                 band, gap_open, want_cigar, zdrop=zdrop,
+                                                 zdrop_rule=zdrop_rule)
     return int(res.scores[0]), res.cigar(0), int(res.query_ends[0]), int(res.target_ends[0])
 
 
@@ -707,7 +729,8 @@ class DevicePlan:
 
     def __init__(self, aligner: Aligner, batch, type, match, mismatch, gap, want_cigar=True, device=None,
                  workspace_budget: int = 0, gap_open=None, flags: int = 0, inputs=None, records=None, band=None,
-                 _banded_affine: bool = False, _anchored: bool = False, _zdrop=None):
+                 _banded_affine: bool = False, _anchored: bool = False, _zdrop=None,
+                 _zdrop_rule: str = "segment"):
         """gap_open=None: team::Align's linear gap.  gap_open=o: the affine-gap
         extension (ta_affine_plan_*) with gap_extend = gap.  flags: TA_PLAN_*
         kernel selection (tests / measurements; same results).  inputs: the
@@ -733,6 +756,8 @@ class DevicePlan:
         self.banded = band is not None
         self.anchored = _anchored
         self.zdrop = _check_zdrop(_zdrop) if _anchored else None
+        self.zdrop_rule = _zdrop_rule
+        rule = _check_zdrop_rule(_zdrop_rule)
         family = ("ta_anchored_plan_" if _anchored else "ta_banded_affine_plan_" if self.affine and self.banded else
                   "ta_affine_plan_" if self.affine else "ta_banded_plan_" if self.banded else "ta_plan_")
         self._fn = lambda name: getattr(L, name.replace("ta_plan_", family))
@@ -742,7 +767,9 @@ class DevicePlan:
         if self.banded:
             self.band = _band_array(band, self.P)
             extra = (_p(self.band if self.band.size else np.zeros(1, np.uint32), C.c_uint32),)
-        create, ztail = ("ta_plan_create", ()) if self.zdrop is None else ("ta_plan_create_zdrop", (self.zdrop,))
+        create, ztail = (("ta_plan_create", ()) if self.zdrop is None else
+                         ("ta_plan_create_zdrop", (self.zdrop,)) if rule == TA_ZDROP_SEGMENT else
+                         ("ta_plan_create_zdrop_rule", (self.zdrop, rule)))
         r = self._fn(create)(aligner.handle, self.P, _p(batch.qlen, C.c_uint32),
                              _p(batch.tlen, C.c_uint32), *extra, *t, *scoring, int(self.want_cigar),
                              workspace_budget, flags, *ztail, C.byref(h))
@@ -795,7 +822,8 @@ class DevicePlan:
 
     @classmethod
     def anchored(cls, aligner: Aligner, batch, match, mismatch, gap, band, gap_open: int = 0, want_cigar=True,
-                 workspace_budget: int = 0, flags: int = 0, device=None, inputs=None, records=None, zdrop=None):
+                 workspace_budget: int = 0, flags: int = 0, device=None, inputs=None, records=None, zdrop=None,
+                 zdrop_rule: str = "segment"):
         """A plan of anchored (free-end) alignment (ta_anchored_plan_*): every
         path starts at (0, 0) and ends at the best in-band interior cell.
         band: an int, or one per pair.  gap_open == 0: the linear kernels
@@ -804,10 +832,12 @@ class DevicePlan:
         band_cells / swept_cells as on a banded plan; ends() returns the goal
         cells; certify() raises.  zdrop=Z (an int >= 0): a z-drop plan
         (ta_anchored_plan_create_zdrop) -- sized as without it; swept_steps()
-        returns the fill steps each pair executed."""
+        returns the fill steps each pair executed.  zdrop_rule="stripe": the
+        row-stripe rule (ta_anchored_plan_create_zdrop_rule), the one to use
+        above band 32; the plan is sized and driven as the segment rule's."""
         return cls(aligner, batch, None, match, mismatch, gap, want_cigar, device, workspace_budget,
                    gap_open=int(gap_open), flags=flags, inputs=inputs, records=records, band=band,
-                   _banded_affine=True, _anchored=True, _zdrop=zdrop)
+                   _banded_affine=True, _anchored=True, _zdrop=zdrop, _zdrop_rule=zdrop_rule)
 
     def swept_steps_async(self):
         """Z-drop plans: enqueue the copy of the last run()'s (or fills') per-pair

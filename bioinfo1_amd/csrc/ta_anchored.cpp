@@ -33,18 +33,28 @@ int ta_anchored_plan_create_zdrop(ta_context* ctx, uint32_t n_pairs, const uint3
                                   const uint32_t* band, int match, int mismatch, int gap_open, int gap_extend,
                                   int want_cigar, uint64_t budget, uint32_t flags, int32_t zdrop,
                                   ta_anchored_plan** out) {
+    return ta_anchored_plan_create_zdrop_rule(ctx, n_pairs, qlen, tlen, band, match, mismatch, gap_open, gap_extend,
+                                              want_cigar, budget, flags, zdrop, TA_ZDROP_SEGMENT, out);
+}
+
+int ta_anchored_plan_create_zdrop_rule(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
+                                       const uint32_t* band, int match, int mismatch, int gap_open, int gap_extend,
+                                       int want_cigar, uint64_t budget, uint32_t flags, int32_t zdrop, int rule,
+                                       ta_anchored_plan** out) {
     if (!out) return TA_ERR_ARG;
     *out = nullptr;
     if (!ctx) return TA_ERR_ARG;
     if (flags & ~TA_ANCHORED_AFFINE_KERNELS)
         return ta_host::fail(ctx, TA_ERR_ARG, "ta_anchored_plan_create: unknown flag bits");
+    if (rule != TA_ZDROP_SEGMENT && rule != TA_ZDROP_STRIPE)
+        return ta_host::fail(ctx, TA_ERR_ARG, "ta_anchored_plan_create: unknown z-drop rule");
     auto* pl = new ta_anchored_plan();
     pl->ctx = ctx;
     const bool affine = gap_open != 0 || (flags & TA_ANCHORED_AFFINE_KERNELS);
     const int r = affine ? ta_host::anchored_affine_create(ctx, n_pairs, qlen, tlen, band, match, mismatch, gap_open,
-                                                           gap_extend, want_cigar, budget, zdrop, &pl->aff)
+                                                           gap_extend, want_cigar, budget, zdrop, rule, &pl->aff)
                          : ta_host::anchored_linear_create(ctx, n_pairs, qlen, tlen, band, match, mismatch,
-                                                           gap_extend, want_cigar, budget, zdrop, &pl->lin);
+                                                           gap_extend, want_cigar, budget, zdrop, rule, &pl->lin);
     if (r != TA_OK) {
         delete pl;
         return r;
@@ -127,13 +137,28 @@ int ta_align_batch_anchored_zdrop(ta_context* ctx, uint32_t n_pairs, const char*
                                   int gap_extend, int want_cigar, int32_t* score, uint32_t* query_end,
                                   uint32_t* target_end, char* arena, uint64_t arena_bytes, uint64_t* cigar_off,
                                   uint32_t* cigar_len, int32_t zdrop, uint32_t* swept_steps) {
+    return ta_align_batch_anchored_zdrop_rule(ctx, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, band, match, mismatch,
+                                              gap_open, gap_extend, want_cigar, score, query_end, target_end, arena,
+                                              arena_bytes, cigar_off, cigar_len, zdrop, TA_ZDROP_SEGMENT, swept_steps);
+}
+
+int ta_align_batch_anchored_zdrop_rule(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
+                                       const uint32_t* qlen, const char* tbytes, const uint64_t* toff,
+                                       const uint32_t* tlen, const uint32_t* band, int match, int mismatch,
+                                       int gap_open, int gap_extend, int want_cigar, int32_t* score,
+                                       uint32_t* query_end, uint32_t* target_end, char* arena, uint64_t arena_bytes,
+                                       uint64_t* cigar_off, uint32_t* cigar_len, int32_t zdrop, int rule,
+                                       uint32_t* swept_steps) {
+    if (!ctx) return TA_ERR_ARG;
+    if (rule != TA_ZDROP_SEGMENT && rule != TA_ZDROP_STRIPE)
+        return ta_host::fail(ctx, TA_ERR_ARG, "ta_align_batch_anchored: unknown z-drop rule");
     if (gap_open != 0)
         return ta_host::anchored_affine_batch(ctx, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, band, match, mismatch,
                                               gap_open, gap_extend, want_cigar, score, query_end, target_end, arena,
-                                              arena_bytes, cigar_off, cigar_len, zdrop, swept_steps);
+                                              arena_bytes, cigar_off, cigar_len, zdrop, rule, swept_steps);
     return ta_host::anchored_linear_batch(ctx, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, band, match, mismatch,
                                           gap_extend, want_cigar, score, query_end, target_end, arena, arena_bytes,
-                                          cigar_off, cigar_len, zdrop, swept_steps);
+                                          cigar_off, cigar_len, zdrop, rule, swept_steps);
 }
 
 }  // extern "C"

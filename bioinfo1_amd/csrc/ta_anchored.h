@@ -19,14 +19,15 @@ namespace ta_host {
 
 // As ta_banded_plan_create / ta_banded_affine_plan_create without `type` and `flags`.
 // zdrop >= 0: a z-drop plan (the DROP fills); zdrop < 0: the plain anchored plan.
+// zdrop_rule: TA_ZDROP_SEGMENT or TA_ZDROP_STRIPE (checked by the caller), which fills a z-drop plan runs.
 TA_ANCHORED_LOCAL int anchored_linear_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen,
                                              const uint32_t* tlen, const uint32_t* band, int match, int mismatch,
                                              int gap, int want_cigar, uint64_t budget, int32_t zdrop,
-                                             ta_banded_plan** out);
+                                             int zdrop_rule, ta_banded_plan** out);
 TA_ANCHORED_LOCAL int anchored_affine_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen,
                                              const uint32_t* tlen, const uint32_t* band, int match, int mismatch,
                                              int gap_open, int gap_extend, int want_cigar, uint64_t budget,
-                                             int32_t zdrop, ta_banded_affine_plan** out);
+                                             int32_t zdrop, int zdrop_rule, ta_banded_affine_plan** out);
 // Enqueue the copy of the plan's goal cells (the last execution's) on `stream`.
 TA_ANCHORED_LOCAL int anchored_linear_ends(ta_banded_plan* pl, uint32_t* query_end_dev, uint32_t* target_end_dev,
                                            void* stream);
@@ -43,13 +44,13 @@ TA_ANCHORED_LOCAL int anchored_linear_batch(ta_context* ctx, uint32_t n_pairs, c
                                             int gap, int want_cigar, int32_t* score, uint32_t* query_end,
                                             uint32_t* target_end, char* arena, uint64_t arena_bytes,
                                             uint64_t* cigar_off, uint32_t* cigar_len, int32_t zdrop,
-                                            uint32_t* swept_steps);
+                                            int zdrop_rule, uint32_t* swept_steps);
 TA_ANCHORED_LOCAL int anchored_affine_batch(ta_context* ctx, uint32_t n_pairs, const char* qb, const uint64_t* qoff,
                                             const uint32_t* qlen, const char* tbytes, const uint64_t* toff,
                                             const uint32_t* tlen, const uint32_t* band, int match, int mismatch,
                                             int gap_open, int gap_extend, int want_cigar, int32_t* score,
                                             uint32_t* query_end, uint32_t* target_end, char* arena,
                                             uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
-                                            int32_t zdrop, uint32_t* swept_steps);
+                                            int32_t zdrop, int zdrop_rule, uint32_t* swept_steps);
 
 }  // namespace ta_host

@@ -80,8 +80,10 @@ struct BandArgs {
 //   QDASH  some query row of this pass is '-' (its vertical gap steps are free)
 //   DROP   z-drop (kAnchored only): every kDropSteps steps, and at the pass's
 //          last step, the wave compares the segment's best H with the running best and leaves
-//          the step loop when it has fallen more than Z below it (drop: in / out, see DropIO)
-template <int MODE, bool CIGAR, bool QDASH, bool DROP = false>
+//          the step loop when it has fallen more than Z below it (drop: in / out, see DropIO).
+//          kDropStripe: at the same steps the wave applies the row-stripe rule
+//          to the lanes whose stripe is complete, and the goal ignores the lanes below the drop
+template <int MODE, bool CIGAR, bool QDASH, int DROP = kNoDrop>
 __device__ __forceinline__ PassOut band_pass(const BandArgs& a, const uint8_t* Q, const uint8_t* T, uint32_t n,
                                              uint32_t m, uint32_t w, uint32_t pass, bool last_pass, uint32_t* prow,
                                              int32_t* B, int lane, DropIO* drop = nullptr) {
@@ -229,7 +231,7 @@ __device__ __forceinline__ PassOut band_pass(const BandArgs& a, const uint8_t* Q
                     bestkey = stepkey;
                     bestj = (uint32_t)j;
                 }
-                if constexpr (DROP) segkey = max(segkey, stepkey);
+                if constexpr (DROP == kDropSegment) segkey = max(segkey, stepkey);
             }
             if (MODE == kSemi && last_pass) {  // row n is register nv-1 of lane nl-1
                 const int rv = select_row<R>(H, nv - 1);
@@ -251,10 +253,39 @@ __device__ __forceinline__ PassOut band_pass(const BandArgs& a, const uint8_t* Q
     const uint32_t u0 = (uint32_t)min(max(t_in, 0), (int)steps);
     const uint32_t u1 = (uint32_t)min(max(t_out, (int)u0), (int)steps);
     uint32_t t = 0;
-    if constexpr (!DROP) {
+    uint32_t nl_goal = nl;  // the lanes whose stripes exist for the goal (the stripe rule cuts it)
+    if constexpr (DROP == kNoDrop) {
         for (; t < u0; ++t) step(t, std::true_type{});
         for (; t < u1; ++t) step(t, std::false_type{});
         for (; t < steps; ++t) step(t, std::true_type{});
+    } else if constexpr (DROP == kDropStripe) {
+        // The row-stripe rule.  The lane's stripe is complete once step tdone has run
+        // (ta_layout.h band_stripe_tau_done); tdone strictly increases with the lane, so the complete
+        // stripes are a prefix of the lanes in use, and the lane's bestkey is then final:
+        // S = the stripe's best H, floored at -1 as every key is.
+        const uint32_t i_last = min(n, row_base + (uint32_t)lane * R + R);
+        const uint32_t tdone = min(m, i_last + (uint32_t)hi) - c0 + (uint32_t)lane;
+        while (t < steps) {
+            const uint32_t tend = min(steps, t + (uint32_t)kDropSteps);  // (t is a multiple of kDropSteps here)
+            for (const uint32_t e1 = min(u0, tend); t < e1; ++t) step(t, std::true_type{});
+            for (const uint32_t e2 = min(u1, tend); t < e2; ++t) step(t, std::false_type{});
+            for (; t < tend; ++t) step(t, std::true_type{});
+            // Each lane's B: the best of the passes above and of the stripes above it in this pass
+            // (an exclusive prefix max; the lanes not complete contribute nothing and are not tested).
+            // The first lane that fails is the sequential scan's drop: B is right up to it.  A stripe
+            // tested at an earlier boundary is tested again with the same operands.
+            const bool fin = ((uint32_t)lane < nl) & (tdone < t);
+            const int S = max(bestkey >> 4, -1);
+            const int Bl = max(drop->best, wave_prefix_max_excl(fin ? S : INT_MIN));
+            const uint64_t dm = ballot(fin & (Bl >= drop->z) & (S < Bl - drop->z));  // (0 <= Bl < 2^26, 0 <= Z: no overflow)
+            if (dm) {  // an SGPR pair: a scalar branch
+                drop->dropped = true;
+                drop->lane = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(dm));
+                nl_goal = (uint32_t)drop->lane + 1;  // the stripes after it do not exist, computed or not
+                break;
+            }
+        }
+        drop->steps += t;
     } else {
         // The same three ranges, cut at the segment boundaries (the unmasked body stays unmasked).
         while (t < steps) {
@@ -282,7 +313,7 @@ __device__ __forceinline__ PassOut band_pass(const BandArgs& a, const uint8_t* Q
     PassOut o{kFloor, 0, 0, kFloor, 0, 0};
     if (ARGMAX) {
         // h first over lanes (the row tag only orders rows inside a lane), then the first lane
-        const int hk = (uint32_t)lane < nl ? (bestkey >> 4) : INT_MIN;
+        const int hk = (uint32_t)lane < nl_goal ? (bestkey >> 4) : INT_MIN;
         const int mx = wave_max(hk);
         const int fl = first_lane(hk == mx);
         const int key = rdlane(bestkey, fl);
@@ -318,8 +349,14 @@ __device__ __forceinline__ PassOut band_pass(const BandArgs& a, const uint8_t* Q
 }
 
 // (the anchored score-only fill is held to the local one's waves per SIMD; 0: no bound)
-template <int MODE, bool CIGAR, bool DROP = false>
-__global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 4 : 0) void banded_fill_kernel(BandArgs a) {
+// MODE_ == kAnchoredStripe (with DROP): the kAnchored fill under the row-stripe z-drop rule.
+// It is an instantiation of this template, not a wrapper around a shared body, so that the other
+// instantiations keep their names and, instruction for instruction, their code.
+template <int MODE_, bool CIGAR, bool DROP_ = false>
+__global__ __launch_bounds__(kBlock, ((MODE_ == kAnchored || MODE_ == kAnchoredStripe) && !CIGAR) ? 4 : 0) void banded_fill_kernel(BandArgs a) {
+    constexpr int MODE = MODE_ == kAnchoredStripe ? (int)kAnchored : MODE_;
+    constexpr int DROP = !DROP_ ? kNoDrop : MODE_ == kAnchoredStripe ? kDropStripe : kDropSegment;
+    static_assert(MODE_ != kAnchoredStripe || DROP_, "the stripe fill is a z-drop fill");
     const int lane = threadIdx.x & 63;
     const uint32_t widx = wave_id();
     if (widx >= a.count) return;  // wave-uniform
@@ -345,7 +382,7 @@ __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 4 : 0) void
             a.target_begin[p] = tb;
             a.goal_i[p] = gi;
             a.goal_j[p] = gj;
-            if constexpr (DROP) a.swept[p] = 0;
+            if constexpr (DROP != kNoDrop) a.swept[p] = 0;
         }
         return;
     }
@@ -361,14 +398,14 @@ __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 4 : 0) void
     int best_h = ((MODE == kSemi && (int)m <= hi) || MODE == kAnchored) ? 0 : kFloor;
     uint32_t best_i = 0, best_j = (MODE == kSemi) ? m : 0;
     int corner = 0;
-    DropIO drop{0, a.zdrop, 0u, false};
+    DropIO drop{0, a.zdrop, 0u, false, 0};
     for (uint32_t pass = 0; pass < passes; ++pass) {
         const bool last_pass = pass + 1 == passes;
         bool dash = false;
         const uint32_t row0 = pass * kPassRows + (uint32_t)lane * kRows;
 #pragma unroll
         for (int r = 0; r < kRows; ++r) dash |= (row0 + r < n) && Q[row0 + r] == '-';
-        if constexpr (DROP) drop.best = best_h;  // the best of the passes above
+        if constexpr (DROP != kNoDrop) drop.best = best_h;  // the best of the passes above
         const PassOut o = __ballot(dash) ? band_pass<MODE, CIGAR, true, DROP>(a, Q, T, n, m, w, pass, last_pass, prow, B, lane, &drop)
                                          : band_pass<MODE, CIGAR, false, DROP>(a, Q, T, n, m, w, pass, last_pass, prow, B, lane, &drop);
         if (MODE != kGlobal && o.h > best_h) {  // strict: the upper pass wins ties
@@ -376,7 +413,7 @@ __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 4 : 0) void
             best_i = o.i;
             best_j = o.j;
         }
-        if constexpr (DROP) {
+        if constexpr (DROP != kNoDrop) {
             if (drop.dropped) break;  // the passes below do not exist (wave-uniform; nobody waits on this wave)
         }
         if (MODE == kSemi && last_pass) {  // row n after column m (:271-278): (n, 0) first, cost 0
@@ -400,7 +437,7 @@ __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 4 : 0) void
         a.target_begin[p] = (MODE == kLocal) ? best_j + 1 : 0;  // :117-121 / :197-199 / :283-285
         a.goal_i[p] = (MODE == kGlobal) ? n : best_i;
         a.goal_j[p] = (MODE == kGlobal) ? m : best_j;
-        if constexpr (DROP) a.swept[p] = drop.steps;
+        if constexpr (DROP != kNoDrop) a.swept[p] = drop.steps;
     }
 }
 
@@ -517,12 +554,15 @@ __global__ __launch_bounds__(kBlock) void banded_traceback_kernel(BandArgs a) {
 
 inline dim3 band_grid(uint32_t waves) { return dim3((waves + kWavesPerBlock - 1) / kWavesPerBlock); }
 
-hipError_t launch_banded_fill(int mode, bool cigar, const BandArgs& a, hipStream_t s) {
+hipError_t launch_banded_fill(int mode, bool cigar, int zdrop_rule, const BandArgs& a, hipStream_t s) {
     if (a.count == 0) return hipSuccess;
     const dim3 g = band_grid(a.count), b(kBlock);
     if (a.zdrop >= 0) {  // z-drop plans: anchored only
         if (mode != kAnchored || !a.swept) return hipErrorInvalidValue;
-        if (cigar) hipLaunchKernelGGL((banded_fill_kernel<kAnchored, true, true>), g, b, 0, s, a);
+        if (zdrop_rule == kZdropStripe) {
+            if (cigar) hipLaunchKernelGGL((banded_fill_kernel<kAnchoredStripe, true, true>), g, b, 0, s, a);
+            else hipLaunchKernelGGL((banded_fill_kernel<kAnchoredStripe, false, true>), g, b, 0, s, a);
+        } else if (cigar) hipLaunchKernelGGL((banded_fill_kernel<kAnchored, true, true>), g, b, 0, s, a);
         else hipLaunchKernelGGL((banded_fill_kernel<kAnchored, false, true>), g, b, 0, s, a);
         return hipGetLastError();
     }
@@ -623,7 +663,7 @@ int ta_banded_plan::exec_chunk(ta_banded_plan* pl, const ta_device_io* io, hipSt
     a.swept = pl->d_swept;
     if (fill) {
         roctxRangePushA("ta banded fill");
-        TA_HIP(ctx, ta::launch_banded_fill(h.type, h.want_cigar, a, s));
+        TA_HIP(ctx, ta::launch_banded_fill(h.type, h.want_cigar, h.zdrop_rule, a, s));
         roctxRangePop();
     }
     if (trace && h.want_cigar) {
@@ -715,7 +755,7 @@ namespace ta_host {
 
 int anchored_linear_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
                            const uint32_t* band, int match, int mismatch, int gap, int want_cigar, uint64_t budget,
-                           int32_t zdrop, ta_banded_plan** out) {
+                           int32_t zdrop, int zdrop_rule, ta_banded_plan** out) {
     if (!out) return TA_ERR_ARG;
     *out = nullptr;
     if (int r = band_check_args(ctx, n_pairs, qlen, tlen, band, TA_GLOBAL, match, mismatch, gap)) return r;
@@ -723,7 +763,7 @@ int anchored_linear_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* ql
     auto* pl = new ta_banded_plan();
     pl->ctx = ctx;
     ta::build_band_plan(pl->h, n_pairs, qlen, tlen, band, ta::kAnchored, match, mismatch, gap, want_cigar != 0,
-                        budget ? budget : default_budget(ctx), zdrop);
+                        budget ? budget : default_budget(ctx), zdrop, zdrop_rule);
     return plan_create_block(pl, "ta_anchored_plan_create: ", out);
 }
 
@@ -739,7 +779,8 @@ int anchored_linear_batch(ta_context* ctx, uint32_t n_pairs, const char* qb, con
                           const uint32_t* qlen, const char* tbytes, const uint64_t* toff, const uint32_t* tlen,
                           const uint32_t* band, int match, int mismatch, int gap, int want_cigar, int32_t* score,
                           uint32_t* query_end, uint32_t* target_end, char* arena, uint64_t arena_bytes,
-                          uint64_t* cigar_off, uint32_t* cigar_len, int32_t zdrop, uint32_t* swept_steps) {
+                          uint64_t* cigar_off, uint32_t* cigar_len, int32_t zdrop, int zdrop_rule,
+                          uint32_t* swept_steps) {
     uint64_t qend = 0, tend = 0;
     if (int r = check_host_batch(ctx, TA_GLOBAL, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, want_cigar, arena,
                                  cigar_off, cigar_len, &qend, &tend))
@@ -756,7 +797,7 @@ int anchored_linear_batch(ta_context* ctx, uint32_t n_pairs, const char* qb, con
     // everything in one chunk while the codes take at most 1 GiB (no device query per call)
     const uint64_t budget = need <= (1ull << 30) ? std::max<uint64_t>(need, 1) : default_budget(ctx);
     ta::build_band_plan(pl.h, n_pairs, qlen, tlen, band, ta::kAnchored, match, mismatch, gap, want_cigar != 0, budget,
-                        zdrop);
+                        zdrop, zdrop_rule);
     if (int r = host_batch(ctx, pl, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
                            nullptr, arena, arena_bytes, cigar_off, cigar_len))
         return r;

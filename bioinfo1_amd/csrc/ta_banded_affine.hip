@@ -89,7 +89,8 @@ struct BandAffArgs {
 // One pass = rows row_base+1 .. row_base+nrows against the columns c0 .. c1.
 //   QDASH  some query row of this pass is '-' (its vertical gap steps are free)
 //   DROP   z-drop (kAnchored only), as ta_banded.hip band_pass
-template <int MODE, bool CIGAR, bool QDASH, bool DROP = false>
+//          (kDropStripe: the row-stripe rule)
+template <int MODE, bool CIGAR, bool QDASH, int DROP = kNoDrop>
 __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uint8_t* Q, const uint8_t* T, uint32_t n,
                                                  uint32_t m, uint32_t w, uint32_t pass, bool last_pass, uint2* prow,
                                                  int2* B, int lane, DropIO* drop = nullptr) {
@@ -263,7 +264,7 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
                     bestkey = stepkey;
                     bestj = (uint32_t)j;
                 }
-                if constexpr (DROP) segkey = max(segkey, stepkey);
+                if constexpr (DROP == kDropSegment) segkey = max(segkey, stepkey);
             }
             if constexpr (MODE == kSemi) {
                 if (last_pass) {  // row n is register nv-1 of lane nl-1
@@ -287,10 +288,34 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
     const uint32_t u0 = (uint32_t)min(max(t_in, 0), (int)steps);
     const uint32_t u1 = (uint32_t)min(max(t_out, (int)u0), (int)steps);
     uint32_t t = 0;
-    if constexpr (!DROP) {
+    uint32_t nl_goal = nl;  // the lanes whose stripes exist for the goal (the stripe rule cuts it)
+    if constexpr (DROP == kNoDrop) {
         for (; t < u0; ++t) step(t, std::true_type{});
         for (; t < u1; ++t) step(t, std::false_type{});
         for (; t < steps; ++t) step(t, std::true_type{});
+    } else if constexpr (DROP == kDropStripe) {
+        // The row-stripe rule, as ta_banded.hip band_pass: the complete stripes are a prefix of the
+        // lanes in use, each lane's B is the best above it (exclusive prefix max), the first lane
+        // that fails is the drop.
+        const uint32_t i_last = min(n, row_base + (uint32_t)lane * R + R);
+        const uint32_t tdone = min(m, i_last + (uint32_t)hi) - c0 + (uint32_t)lane;
+        while (t < steps) {
+            const uint32_t tend = min(steps, t + (uint32_t)kDropSteps);  // (t is a multiple of kDropSteps here)
+            for (const uint32_t e1 = min(u0, tend); t < e1; ++t) step(t, std::true_type{});
+            for (const uint32_t e2 = min(u1, tend); t < e2; ++t) step(t, std::false_type{});
+            for (; t < tend; ++t) step(t, std::true_type{});
+            const bool fin = ((uint32_t)lane < nl) & (tdone < t);
+            const int S = max(bestkey >> 4, -1);
+            const int Bl = max(drop->best, wave_prefix_max_excl(fin ? S : INT_MIN));
+            const uint64_t dm = ballot(fin & (Bl >= drop->z) & (S < Bl - drop->z));  // (0 <= Bl < 2^26, 0 <= Z: no overflow)
+            if (dm) {  // an SGPR pair: a scalar branch
+                drop->dropped = true;
+                drop->lane = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(dm));
+                nl_goal = (uint32_t)drop->lane + 1;  // the stripes after it do not exist, computed or not
+                break;
+            }
+        }
+        drop->steps += t;
     } else {
         // The same three ranges, cut at the segment boundaries (the unmasked body stays unmasked).
         while (t < steps) {
@@ -315,7 +340,7 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
     PassOut o{kFloor, 0, 0, kFloor, 0, 0};
     if constexpr (ARGMAX) {
         // h first over lanes (the row tag only orders rows inside a lane), then the first lane
-        const int hk = (uint32_t)lane < nl ? (bestkey >> 4) : INT_MIN;
+        const int hk = (uint32_t)lane < nl_goal ? (bestkey >> 4) : INT_MIN;
         const int mx = wave_max(hk);
         const int fl = first_lane(hk == mx);
         const int key = rdlane(bestkey, fl);
@@ -351,8 +376,14 @@ __device__ __forceinline__ PassOut band_aff_pass(const BandAffArgs& a, const uin
 }
 
 // (the anchored score-only fill is held to the local one's waves per SIMD; 0: no bound)
-template <int MODE, bool CIGAR, bool DROP = false>
-__global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 3 : 0) void banded_affine_fill_kernel(BandAffArgs a) {
+// MODE_ == kAnchoredStripe (with DROP): the kAnchored fill under the row-stripe z-drop rule.
+// It is an instantiation of this template, not a wrapper around a shared body, so that the other
+// instantiations keep their names and, instruction for instruction, their code.
+template <int MODE_, bool CIGAR, bool DROP_ = false>
+__global__ __launch_bounds__(kBlock, ((MODE_ == kAnchored || MODE_ == kAnchoredStripe) && !CIGAR) ? 3 : 0) void banded_affine_fill_kernel(BandAffArgs a) {
+    constexpr int MODE = MODE_ == kAnchoredStripe ? (int)kAnchored : MODE_;
+    constexpr int DROP = !DROP_ ? kNoDrop : MODE_ == kAnchoredStripe ? kDropStripe : kDropSegment;
+    static_assert(MODE_ != kAnchoredStripe || DROP_, "the stripe fill is a z-drop fill");
     const int lane = threadIdx.x & 63;
     const uint32_t widx = wave_id();
     if (widx >= a.count) return;  // wave-uniform
@@ -378,7 +409,7 @@ __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 3 : 0) void
             a.target_begin[p] = tb;
             a.goal_i[p] = gi;
             a.goal_j[p] = gj;
-            if constexpr (DROP) a.swept[p] = 0;
+            if constexpr (DROP != kNoDrop) a.swept[p] = 0;
         }
         return;
     }
@@ -394,14 +425,14 @@ __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 3 : 0) void
     int best_h = ((MODE == kSemi && (int)m <= hi) || MODE == kAnchored) ? 0 : kFloor;
     uint32_t best_i = 0, best_j = (MODE == kSemi) ? m : 0;
     int corner = 0;
-    DropIO drop{0, a.zdrop, 0u, false};
+    DropIO drop{0, a.zdrop, 0u, false, 0};
     for (uint32_t pass = 0; pass < passes; ++pass) {
         const bool last_pass = pass + 1 == passes;
         bool dash = false;
         const uint32_t row0 = pass * kPassRows + (uint32_t)lane * kRows;
 #pragma unroll
         for (int r = 0; r < kRows; ++r) dash |= (row0 + r < n) && Q[row0 + r] == '-';
-        if constexpr (DROP) drop.best = best_h;  // the best of the passes above
+        if constexpr (DROP != kNoDrop) drop.best = best_h;  // the best of the passes above
         const PassOut o =
             __ballot(dash)
                 ? band_aff_pass<MODE, CIGAR, true, DROP>(a, Q, T, n, m, w, pass, last_pass, prow, B, lane, &drop)
@@ -411,7 +442,7 @@ __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 3 : 0) void
             best_i = o.i;
             best_j = o.j;
         }
-        if constexpr (DROP) {
+        if constexpr (DROP != kNoDrop) {
             if (drop.dropped) break;  // the passes below do not exist (wave-uniform; nobody waits on this wave)
         }
         if (MODE == kSemi && last_pass) {  // row n after column m (:271-278): (n, 0) first, cost 0
@@ -435,7 +466,7 @@ __global__ __launch_bounds__(kBlock, (MODE == kAnchored && !CIGAR) ? 3 : 0) void
         a.target_begin[p] = (MODE == kLocal) ? best_j + 1 : 0;  // :117-121 / :197-199 / :283-285
         a.goal_i[p] = (MODE == kGlobal) ? n : best_i;
         a.goal_j[p] = (MODE == kGlobal) ? m : best_j;
-        if constexpr (DROP) a.swept[p] = drop.steps;
+        if constexpr (DROP != kNoDrop) a.swept[p] = drop.steps;
     }
 }
 
@@ -467,12 +498,15 @@ __global__ __launch_bounds__(kBlock) void banded_affine_traceback_kernel(BandAff
 
 inline dim3 band_aff_grid(uint32_t waves) { return dim3((waves + kWavesPerBlock - 1) / kWavesPerBlock); }
 
-hipError_t launch_banded_affine_fill(int mode, bool cigar, const BandAffArgs& a, hipStream_t s) {
+hipError_t launch_banded_affine_fill(int mode, bool cigar, int zdrop_rule, const BandAffArgs& a, hipStream_t s) {
     if (a.count == 0) return hipSuccess;
     const dim3 g = band_aff_grid(a.count), b(kBlock);
     if (a.zdrop >= 0) {  // z-drop plans: anchored only
         if (mode != kAnchored || !a.swept) return hipErrorInvalidValue;
-        if (cigar) hipLaunchKernelGGL((banded_affine_fill_kernel<kAnchored, true, true>), g, b, 0, s, a);
+        if (zdrop_rule == kZdropStripe) {
+            if (cigar) hipLaunchKernelGGL((banded_affine_fill_kernel<kAnchoredStripe, true, true>), g, b, 0, s, a);
+            else hipLaunchKernelGGL((banded_affine_fill_kernel<kAnchoredStripe, false, true>), g, b, 0, s, a);
+        } else if (cigar) hipLaunchKernelGGL((banded_affine_fill_kernel<kAnchored, true, true>), g, b, 0, s, a);
         else hipLaunchKernelGGL((banded_affine_fill_kernel<kAnchored, false, true>), g, b, 0, s, a);
         return hipGetLastError();
     }
@@ -578,7 +612,7 @@ int ta_banded_affine_plan::exec_chunk(ta_banded_affine_plan* pl, const ta_device
     a.swept = pl->d_swept;
     if (fill) {
         roctxRangePushA("ta banded affine fill");
-        TA_HIP(ctx, ta::launch_banded_affine_fill(h.type, h.want_cigar, a, s));
+        TA_HIP(ctx, ta::launch_banded_affine_fill(h.type, h.want_cigar, h.zdrop_rule, a, s));
         roctxRangePop();
     }
     if (trace && h.want_cigar) {
@@ -677,7 +711,7 @@ namespace ta_host {
 
 int anchored_affine_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
                            const uint32_t* band, int match, int mismatch, int gap_open, int gap_extend, int want_cigar,
-                           uint64_t budget, int32_t zdrop, ta_banded_affine_plan** out) {
+                           uint64_t budget, int32_t zdrop, int zdrop_rule, ta_banded_affine_plan** out) {
     if (!out) return TA_ERR_ARG;
     *out = nullptr;
     if (int r = band_aff_check_args(ctx, n_pairs, qlen, tlen, band, TA_GLOBAL, match, mismatch, gap_open, gap_extend))
@@ -686,7 +720,7 @@ int anchored_affine_create(ta_context* ctx, uint32_t n_pairs, const uint32_t* ql
     auto* pl = new ta_banded_affine_plan();
     pl->ctx = ctx;
     ta::build_band_affine_plan(pl->h, n_pairs, qlen, tlen, band, ta::kAnchored, match, mismatch, gap_open, gap_extend,
-                               want_cigar != 0, budget ? budget : default_budget(ctx), zdrop);
+                               want_cigar != 0, budget ? budget : default_budget(ctx), zdrop, zdrop_rule);
     return plan_create_block(pl, "ta_anchored_plan_create: ", out);
 }
 
@@ -703,7 +737,7 @@ int anchored_affine_batch(ta_context* ctx, uint32_t n_pairs, const char* qb, con
                           const uint32_t* band, int match, int mismatch, int gap_open, int gap_extend, int want_cigar,
                           int32_t* score, uint32_t* query_end, uint32_t* target_end, char* arena,
                           uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len, int32_t zdrop,
-                          uint32_t* swept_steps) {
+                          int zdrop_rule, uint32_t* swept_steps) {
     uint64_t qend = 0, tend = 0;
     if (int r = check_host_batch(ctx, TA_GLOBAL, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, want_cigar, arena,
                                  cigar_off, cigar_len, &qend, &tend))
@@ -721,7 +755,7 @@ int anchored_affine_batch(ta_context* ctx, uint32_t n_pairs, const char* qb, con
     // everything in one chunk while the codes take at most 1 GiB (no device query per call)
     const uint64_t budget = need <= (1ull << 30) ? std::max<uint64_t>(need, 1) : default_budget(ctx);
     ta::build_band_affine_plan(pl.h, n_pairs, qlen, tlen, band, ta::kAnchored, match, mismatch, gap_open, gap_extend,
-                               want_cigar != 0, budget, zdrop);
+                               want_cigar != 0, budget, zdrop, zdrop_rule);
     if (int r = host_batch(ctx, pl, n_pairs, qb, qoff, qlen, tbytes, toff, tlen, qend, tend, want_cigar, score,
                            nullptr, arena, arena_bytes, cigar_off, cigar_len))
         return r;

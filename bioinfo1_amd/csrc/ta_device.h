@@ -48,6 +48,19 @@ __device__ __forceinline__ int wave_max(int v) {
     return v;
 }
 
+// Exclusive prefix max over the lanes below (lane 0: INT_MIN): the DPP inclusive scan (row_shr
+// 1, 2, 4, 8 inside each row of 16 lanes, then row_bcast 15 / 31 across the rows), shifted down
+// one lane.  A lane without a source keeps `old` = INT_MIN.  Must run with all 64 lanes enabled.
+__device__ __forceinline__ int wave_prefix_max_excl(int v) {
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x111, 0xF, 0xF, false));
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x112, 0xF, 0xF, false));
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x114, 0xF, 0xF, false));
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x118, 0xF, 0xF, false));
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x142, 0xA, 0xF, false));  // row_bcast:15 -> rows 1, 3
+    v = max(v, __builtin_amdgcn_update_dpp(INT_MIN, v, 0x143, 0xC, 0xF, false));  // row_bcast:31 -> rows 2, 3
+    return __builtin_amdgcn_update_dpp(INT_MIN, v, 0x138, 0xF, 0xF, false);       // wave_shr:1
+}
+
 __device__ __forceinline__ int first_lane(bool c) {
     const unsigned long long b = __ballot(c);
     return b ? __ffsll((long long)b) - 1 : -1;
@@ -397,7 +410,12 @@ struct DropIO {
     int z;           // in: Z >= 0
     uint32_t steps;  // in / out: the fill steps executed so far
     bool dropped;    // out: the pair dropped in this pass
+    int lane;        // out, the stripe rule: the lane whose stripe dropped
 };
+// Which z-drop rule a banded anchored fill applies.
+enum DropRule : int { kNoDrop = 0, kDropSegment = 1, kDropStripe = 2 };
+// A MODE of the banded fill kernels' template only, never of a plan: kAnchored under the stripe rule.
+constexpr int kAnchoredStripe = 4;
 
 }  // namespace
 }  // namespace ta

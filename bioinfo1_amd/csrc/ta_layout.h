@@ -198,6 +198,27 @@ TA_HD inline uint64_t band_drop_swept_steps(uint32_t n, uint32_t m, uint32_t w, 
     }
     return steps;
 }
+// ---- The row-stripe z-drop rule (TA_ZDROP_STRIPE; DEFINED in include/team_align_c.h
+// and restated in tests/anchored_zdrop_stripe_ref.py).  A stripe is the 16 rows one lane
+// of the fill owns: stripe g is rows 16 g + 1 .. min(16 g + 16, n), lane g % 64 of pass
+// g / 64.  The rule is tied to rows; only the step count follows the sweep: the fill
+// tests the rule after every kDropSteps-th step of a pass and after its last step, on
+// the stripes whose last cell has been computed by then.
+constexpr int kZdropSegment = 0, kZdropStripe = 1;  // TA_ZDROP_SEGMENT / TA_ZDROP_STRIPE
+TA_HD inline uint32_t band_stripes(uint32_t n) { return (n + kRows - 1) / kRows; }
+// The step of its pass at which stripe g's last cell (row i_last, column min(m, i_last + hi))
+// is computed; it strictly increases with the lane, and is below band_drop_steps.
+TA_HD inline uint32_t band_stripe_tau_done(uint32_t n, uint32_t m, uint32_t w, uint32_t g) {
+    const uint32_t i_last = n < kRows * g + kRows ? n : kRows * g + kRows;
+    const uint32_t jl = i_last + (uint32_t)band_hi(n, m, w);
+    return (jl < m ? jl : m) - band_c0(n, m, w, g / kWave) + g % kWave;
+}
+// Steps a pair executes when it drops at stripe g; g == band_stripes(n): when nothing drops.
+TA_HD inline uint64_t band_stripe_swept_steps(uint32_t n, uint32_t m, uint32_t w, uint32_t g) {
+    if (n == 0 || m == 0) return 0;
+    if (g >= band_stripes(n)) return band_drop_swept_steps(n, m, w, n_passes(n), 0);
+    return band_drop_swept_steps(n, m, w, g / kWave, band_stripe_tau_done(n, m, w, g) / kDropSteps);
+}
 
 // In-band interior cells (1 <= i <= n, 1 <= j <= m) and the cells the passes sweep.
 TA_HD inline uint64_t band_cells(uint32_t n, uint32_t m, uint32_t w) {

@@ -673,11 +673,13 @@ Assembly assemble_band(P& pl, uint32_t n_pairs, const uint32_t* qlen, const uint
 }  // namespace
 
 void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
-                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget, int32_t zdrop) {
+                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget, int32_t zdrop,
+                     int zdrop_rule) {
     pl = BandPlan{};
     init_plan(pl, n_pairs, qlen, tlen, type, match, mismatch, want_cigar);
     pl.gap = gap;
     pl.zdrop = (type == kAnchored && zdrop >= 0) ? zdrop : -1;
+    pl.zdrop_rule = (pl.zdrop >= 0 && zdrop_rule == kZdropStripe) ? kZdropStripe : kZdropSegment;
     const Assembly as = assemble_band(pl, n_pairs, qlen, tlen, band, budget / 4);
     for (const Cut& c : as.cuts) pl.chunks.push_back({{c.begin, c.count}, c.codes, c.bnd});
     pl.ws_ptr_dwords = as.ws_codes;
@@ -686,12 +688,13 @@ void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const
 
 void build_band_affine_plan(BandAffinePlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
                             const uint32_t* band, int type, int match, int mismatch, int gap_open, int gap_extend,
-                            bool want_cigar, uint64_t budget, int32_t zdrop) {
+                            bool want_cigar, uint64_t budget, int32_t zdrop, int zdrop_rule) {
     pl = BandAffinePlan{};
     init_plan(pl, n_pairs, qlen, tlen, type, match, mismatch, want_cigar);
     pl.open = gap_open;
     pl.extend = gap_extend;
     pl.zdrop = (type == kAnchored && zdrop >= 0) ? zdrop : -1;
+    pl.zdrop_rule = (pl.zdrop >= 0 && zdrop_rule == kZdropStripe) ? kZdropStripe : kZdropSegment;
     const Assembly as = assemble_band(pl, n_pairs, qlen, tlen, band, budget / 8);
     for (const Cut& c : as.cuts) pl.chunks.push_back({{c.begin, c.count}, c.codes, c.bnd});
     pl.ws_ptr_entries = as.ws_codes;

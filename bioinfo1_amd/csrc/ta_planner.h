@@ -144,6 +144,7 @@ void build_affine_plan(AffinePlan& pl, uint32_t n_pairs, const uint32_t* qlen, c
 struct BandPlan : PlanBase {
     int gap = 0;
     int32_t zdrop = -1;  // kAnchored: Z of the z-drop rule, < 0: off (sizes nothing: a drop only leaves workspace unused)
+    int zdrop_rule = kZdropSegment;  // which rule the fills apply (ta_layout.h); the planning is the same for both
     std::vector<uint32_t> band;  // per pair, clamped
     struct Chunk : ChunkSpan {
         uint64_t ptr_dwords, bnd_words;
@@ -157,7 +158,8 @@ struct BandPlan : PlanBase {
 // type: a Mode of ta_layout.h, kAnchored included (sized as global: codes, boundary rows, chunks, slots).
 // zdrop >= 0 (kAnchored only): a z-drop plan; every sized field is the zdrop < 0 plan's.
 void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen, const uint32_t* band,
-                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget, int32_t zdrop = -1);
+                     int type, int match, int mismatch, int gap, bool want_cigar, uint64_t budget, int32_t zdrop = -1,
+                     int zdrop_rule = kZdropSegment);
 
 // Banded affine plan (the banded affine extension of include/team_align_c.h):
 // the banded plan with 8-byte code entries (one uint2 per (pass, swept step,
@@ -165,6 +167,7 @@ void build_band_plan(BandPlan& pl, uint32_t n_pairs, const uint32_t* qlen, const
 struct BandAffinePlan : PlanBase {
     int open = 0, extend = 0;
     int32_t zdrop = -1;  // as BandPlan::zdrop
+    int zdrop_rule = kZdropSegment;  // as BandPlan::zdrop_rule
     std::vector<uint32_t> band;  // per pair, clamped
     struct Chunk : ChunkSpan {
         uint64_t ptr_entries, bnd_entries;
@@ -177,7 +180,8 @@ struct BandAffinePlan : PlanBase {
 // budget = bytes of 4-bit codes (8-byte entries) per chunk (> 0); order and chunking as build_band_plan.
 void build_band_affine_plan(BandAffinePlan& pl, uint32_t n_pairs, const uint32_t* qlen, const uint32_t* tlen,
                             const uint32_t* band, int type, int match, int mismatch, int gap_open, int gap_extend,
-                            bool want_cigar, uint64_t budget, int32_t zdrop = -1);
+                            bool want_cigar, uint64_t budget, int32_t zdrop = -1,
+                            int zdrop_rule = kZdropSegment);
 
 // One contiguous block holding several arrays, each at a 256-byte aligned
 // offset: the plan's per-pair arrays go to the device in one copy.

@@ -244,7 +244,8 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
                           uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end,
                           int32_t* score, char* arena, uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
                           uint32_t flags, ta_pair_info* info, const uint32_t* band, const int* gap_open = nullptr,
-                          bool band_auto = false, bool extend_ends = false, int32_t zdrop = -1);
+                          bool band_auto = false, bool extend_ends = false, int32_t zdrop = -1,
+                          int zdrop_rule = TA_ZDROP_SEGMENT);
 
 int tm_map_batch_x(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes, const uint64_t* off,
                    const uint32_t* len, const tm_options* opt, uint8_t* mapped, uint8_t* strand_fwd, uint32_t* q_begin,
@@ -293,9 +294,20 @@ int tm_map_batch_band_ends_zdrop(tm_context* ctx, const tm_index* idx, uint32_t 
                                  uint32_t* t_end, int32_t* score, char* arena, uint64_t arena_bytes,
                                  uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags, ta_pair_info* info,
                                  uint32_t band, const int* gap_open, int32_t zdrop) {
+    return tm_map_batch_band_ends_zdrop_rule(ctx, idx, n_reads, bytes, off, len, opt, mapped, strand_fwd, q_begin,
+                                             q_end, t_begin, t_end, score, arena, arena_bytes, cigar_off, cigar_len,
+                                             flags, info, band, gap_open, zdrop, TA_ZDROP_SEGMENT);
+}
+
+int tm_map_batch_band_ends_zdrop_rule(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
+                                      const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
+                                      uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin,
+                                      uint32_t* t_end, int32_t* score, char* arena, uint64_t arena_bytes,
+                                      uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags, ta_pair_info* info,
+                                      uint32_t band, const int* gap_open, int32_t zdrop, int zdrop_rule) {
     return map_batch_impl(ctx, idx, n_reads, bytes, off, len, opt, mapped, strand_fwd, q_begin, q_end, t_begin, t_end,
                           score, arena, arena_bytes, cigar_off, cigar_len, flags, info, &band, gap_open, false, true,
-                          zdrop);
+                          zdrop, zdrop_rule);
 }
 
 int tm_map_batch_band_exact(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
@@ -313,9 +325,11 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
                           uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin, uint32_t* t_end,
                           int32_t* score, char* arena, uint64_t arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
                           uint32_t flags, ta_pair_info* info, const uint32_t* band, const int* gap_open,
-                          bool band_auto, bool extend_ends, int32_t zdrop) {
+                          bool band_auto, bool extend_ends, int32_t zdrop, int zdrop_rule) {
     if (!ctx || !idx || !opt) return TM_ERR_ARG;
     if (zdrop >= 0 && !extend_ends) return fail(ctx, TM_ERR_ARG, "--zdrop needs --extend-ends");
+    if (zdrop_rule != TA_ZDROP_SEGMENT && zdrop_rule != TA_ZDROP_STRIPE)
+        return fail(ctx, TM_ERR_ARG, "unknown z-drop rule");
     if (flags & ~TM_MAP_EQX) return fail(ctx, TM_ERR_ARG, "unknown flag");
     if (info && !(flags & TM_MAP_EQX)) return fail(ctx, TM_ERR_ARG, "info needs TM_MAP_EQX");
     const bool eqx = (flags & TM_MAP_EQX) != 0;
@@ -584,10 +598,10 @@ static int map_batch_impl(tm_context* ctx, const tm_index* idx, uint32_t n_reads
             ~Guard() { ta_anchored_plan_destroy(p); }
         } g;
         const std::vector<uint32_t> ebw(P, *band);
-        // (both end plans get Z; zdrop < 0: the plain anchored plan)
-        if (ta_anchored_plan_create_zdrop(ctx->ta, P, eq, et, ebw.data(), opt->match, opt->mismatch,
-                                          gap_open ? *gap_open : 0, opt->gap, opt->want_cigar, budget, 0, zdrop,
-                                          &g.p) != TA_OK)
+        // (both end plans get Z and the rule; zdrop < 0: the plain anchored plan)
+        if (ta_anchored_plan_create_zdrop_rule(ctx->ta, P, eq, et, ebw.data(), opt->match, opt->mismatch,
+                                               gap_open ? *gap_open : 0, opt->gap, opt->want_cigar, budget, 0, zdrop,
+                                               zdrop_rule, &g.p) != TA_OK)
             return fail(ctx, TM_ERR_DEVICE, std::string("ta_anchored_plan_create: ") + ta_last_error(ctx->ta));
         const uint64_t eslots = ta_anchored_plan_cigar_slots_bytes(g.p);
         ctx->plan_stats[1] += ta_anchored_plan_chunks(g.p);
@@ -817,7 +831,7 @@ int tm_map_files(const char* reference_path, const char* reads_path, const tm_op
 static int map_files_impl(const char* reference_path, const char* reads_path, const tm_options* opt,
                           const char* out_path, int device, uint32_t flags, const uint32_t* band,
                           const int* gap_open = nullptr, bool band_auto = false, bool extend_ends = false,
-                          int32_t zdrop = -1);
+                          int32_t zdrop = -1, int zdrop_rule = TA_ZDROP_SEGMENT);
 
 int tm_map_files_x(const char* reference_path, const char* reads_path, const tm_options* opt, const char* out_path,
                    int device, uint32_t flags) {
@@ -842,8 +856,15 @@ int tm_map_files_band_ends(const char* reference_path, const char* reads_path, c
 int tm_map_files_band_ends_zdrop(const char* reference_path, const char* reads_path, const tm_options* opt,
                                  const char* out_path, int device, uint32_t flags, uint32_t band, const int* gap_open,
                                  int32_t zdrop) {
+    return tm_map_files_band_ends_zdrop_rule(reference_path, reads_path, opt, out_path, device, flags, band, gap_open,
+                                             zdrop, TA_ZDROP_SEGMENT);
+}
+
+int tm_map_files_band_ends_zdrop_rule(const char* reference_path, const char* reads_path, const tm_options* opt,
+                                      const char* out_path, int device, uint32_t flags, uint32_t band,
+                                      const int* gap_open, int32_t zdrop, int zdrop_rule) {
     return map_files_impl(reference_path, reads_path, opt, out_path, device, flags, &band, gap_open, false, true,
-                          zdrop);
+                          zdrop, zdrop_rule);
 }
 
 int tm_map_files_band_exact(const char* reference_path, const char* reads_path, const tm_options* opt,
@@ -854,9 +875,10 @@ int tm_map_files_band_exact(const char* reference_path, const char* reads_path, 
 
 static int map_files_impl(const char* reference_path, const char* reads_path, const tm_options* opt,
                           const char* out_path, int device, uint32_t flags, const uint32_t* band, const int* gap_open,
-                          bool band_auto, bool extend_ends, int32_t zdrop) {
+                          bool band_auto, bool extend_ends, int32_t zdrop, int zdrop_rule) {
     if (!reference_path || !reads_path || !opt || !out_path || (flags & ~TM_MAP_EQX)) return TM_ERR_ARG;
     if (zdrop >= 0 && !extend_ends) return TM_ERR_ARG;
+    if (zdrop_rule != TA_ZDROP_SEGMENT && zdrop_rule != TA_ZDROP_STRIPE) return TM_ERR_ARG;
     // (before any file is read: the same rules as tm_map_batch_band_ends)
     if (extend_ends && (!band || band_auto || opt->type != TA_GLOBAL || (flags & TM_MAP_EQX))) return TM_ERR_ARG;
     const bool eqx = (flags & TM_MAP_EQX) != 0;
@@ -919,7 +941,7 @@ static int map_files_impl(const char* reference_path, const char* reads_path, co
         rc = map_batch_impl(ctx, idx, nr, reads.seq.data() + base, off.data(), len.data(), &o, mapped.data(),
                             fwd.data(), qb.data(), qe.data(), tb.data(), te.data(), sc.data(), arena.data(), arena.size(),
                             co.data(), cl.data(), flags, eqx ? info.data() : nullptr, band, gap_open, band_auto,
-                            extend_ends, zdrop);
+                            extend_ends, zdrop, zdrop_rule);
         if (rc) {
             std::fprintf(stderr, "map: %s: %s\n", tm_status_string(rc), tm_last_error(ctx));
             break;

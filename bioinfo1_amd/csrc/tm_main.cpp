@@ -46,6 +46,8 @@ int main(int argc, char** argv) {
     int gap_open = 0;
     bool extend_ends = false;  // --extend-ends (with --band N, -a global): windows extended to the read's ends (not in help())
     int zdrop = -1;  // --zdrop Z (with --extend-ends): both end extensions stop once the end has died (not in help())
+    bool zdrop_rule_given = false;  // --zdrop-rule segment|stripe (with --zdrop): which rule decides the drop (not in help())
+    int zdrop_rule = TA_ZDROP_SEGMENT;
     if (argc < 2) {
         std::fprintf(stderr, "Error: Not enough arguments\n");
         help();
@@ -122,6 +124,16 @@ int main(int argc, char** argv) {
             }
             zdrop = (int)v;
         }
+        else if (!std::strcmp(a, "--zdrop-rule") && more) {
+            const char* v = argv[++i];
+            if (!std::strcmp(v, "segment")) zdrop_rule = TA_ZDROP_SEGMENT;
+            else if (!std::strcmp(v, "stripe")) zdrop_rule = TA_ZDROP_STRIPE;
+            else {
+                std::fprintf(stderr, "Error: --zdrop-rule expects segment or stripe\n");
+                return 1;
+            }
+            zdrop_rule_given = true;
+        }
         else if (!std::strcmp(a, "-s")) std::fprintf(stderr, "note: -s (statistics) is not part of this build\n");
         else if (f1.empty()) f1 = a;
         else if (f2.empty()) f2 = a;
@@ -155,11 +167,16 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "Error: --zdrop requires --extend-ends\n");
         return 1;
     }
-    if (zdrop >= 0 && band > 32)  // (the band caveat: the rule follows the fill's step order)
+    if (zdrop_rule_given && zdrop < 0) {
+        std::fprintf(stderr, "Error: --zdrop-rule requires --zdrop\n");
+        return 1;
+    }
+    // (the band caveat: the segment rule follows the fill's step order; the stripe rule, §3.20, does not)
+    if (zdrop >= 0 && band > 32 && zdrop_rule == TA_ZDROP_SEGMENT)
         std::fprintf(stderr, "warning: --zdrop with --band above 32 can clip a live end longer than 1024 bases at "
                              "row 1024; use --band 32 or less, or a large Z\n");
-    const int r = extend_ends ? tm_map_files_band_ends_zdrop(f1.c_str(), f2.c_str(), &o, "-", device, flags, band,
-                                                             affine ? &gap_open : nullptr, zdrop)
+    const int r = extend_ends ? tm_map_files_band_ends_zdrop_rule(f1.c_str(), f2.c_str(), &o, "-", device, flags, band,
+                                                                  affine ? &gap_open : nullptr, zdrop, zdrop_rule)
                   : band_auto ? tm_map_files_band_exact(f1.c_str(), f2.c_str(), &o, "-", device, flags,
                                                       affine ? &gap_open : nullptr)
                   : affine   ? tm_map_files_band_affine(f1.c_str(), f2.c_str(), &o, "-", device, flags, band, gap_open)

@@ -35,7 +35,8 @@ ABI_SYMBOLS = ["tm_status_string", "tm_last_error", "tm_context_create", "tm_con
                "tm_map_files_x", "tm_map_batch_band", "tm_map_files_band", "tm_map_batch_band_affine",
                "tm_map_files_band_affine", "tm_map_batch_band_exact", "tm_map_files_band_exact",
                "tm_map_batch_band_ends", "tm_map_files_band_ends", "tm_ends_arena_extra",
-               "tm_map_batch_band_ends_zdrop", "tm_map_files_band_ends_zdrop"]
+               "tm_map_batch_band_ends_zdrop", "tm_map_files_band_ends_zdrop",
+               "tm_map_batch_band_ends_zdrop_rule", "tm_map_files_band_ends_zdrop_rule"]
 TM_MAP_EQX = 1
 
 _lib = None
@@ -95,6 +96,8 @@ def lib() -> C.CDLL:
     L.tm_map_files_band_ends.argtypes = L.tm_map_files_band.argtypes + [C.POINTER(C.c_int)]
     L.tm_map_batch_band_ends_zdrop.argtypes = L.tm_map_batch_band_ends.argtypes + [C.c_int32]
     L.tm_map_files_band_ends_zdrop.argtypes = L.tm_map_files_band_ends.argtypes + [C.c_int32]
+    L.tm_map_batch_band_ends_zdrop_rule.argtypes = L.tm_map_batch_band_ends_zdrop.argtypes + [C.c_int]
+    L.tm_map_files_band_ends_zdrop_rule.argtypes = L.tm_map_files_band_ends_zdrop.argtypes + [C.c_int]
     L.tm_ends_arena_extra.restype = C.c_uint64
     L.tm_ends_arena_extra.argtypes = [C.c_uint32, C.c_uint32]
     _lib = L
@@ -264,7 +267,7 @@ class Index:
                         [x.value for x in v]))
 
     def map_batch(self, reads, opt: Options, eqx: bool = False, band=None, gap_open=None,
-                  extend_ends: bool = False, zdrop=None) -> MapResult:
+                  extend_ends: bool = False, zdrop=None, zdrop_rule: str = "segment") -> MapResult:
         """reads: sequences, or a prepared (bytes, off, len) tuple (see soa()).
         eqx: tm_map_batch_x with TM_MAP_EQX -- =/X CIGARs and the info records.
         band: None, or the band of every window (tm_map_batch_band: the banded
@@ -278,9 +281,13 @@ class Index:
         three CIGARs are stitched (tm_map_batch_band_ends).
         zdrop: with extend_ends, Z of the z-drop rule for both ends
         (tm_map_batch_band_ends_zdrop): an end that has died is clipped there
-        and its sweep stops."""
+        and its sweep stops.
+        zdrop_rule: "segment" (the default) or "stripe", only with zdrop: the
+        row-stripe rule (tm_map_batch_band_ends_zdrop_rule), which does not
+        clip a live end at a pass boundary -- the one to use above band 32."""
         L = lib()
         zdrop = _check_zdrop(zdrop, extend_ends)
+        rule = _check_zdrop_rule(zdrop_rule, zdrop)
         if gap_open is not None and band is None:
             raise ValueError("gap_open needs a band: the mapper has no unbanded affine path")
         auto = isinstance(band, str)
@@ -306,6 +313,8 @@ class Index:
                                                       None if gap_open is None else C.byref(C.c_int(int(gap_open))))
                 if zdrop is not None:
                     fn, more = L.tm_map_batch_band_ends_zdrop, more + (zdrop,)
+                    if rule != _align.TA_ZDROP_SEGMENT:
+                        fn, more = L.tm_map_batch_band_ends_zdrop_rule, more + (rule,)
             elif auto:
                 fn, more = L.tm_map_batch_band_exact, (None if gap_open is None else C.byref(C.c_int(int(gap_open))),)
             elif gap_open is None:
@@ -360,15 +369,25 @@ def _check_zdrop(zdrop, extend_ends):
     return _align._check_zdrop(zdrop)
 
 
+def _check_zdrop_rule(zdrop_rule, zdrop) -> int:
+    """"segment" or "stripe" -> TA_ZDROP_*; anything but the default only with zdrop."""
+    rule = _align._check_zdrop_rule(zdrop_rule)
+    if rule != _align.TA_ZDROP_SEGMENT and zdrop is None:
+        raise ValueError("zdrop_rule needs zdrop")
+    return rule
+
+
 def map_files(reference: str, reads: str, out: str = "-", device: int = 0, band=None, gap_open=None,
-              extend_ends: bool = False, zdrop=None, **opts) -> None:
+              extend_ends: bool = False, zdrop=None, zdrop_rule: str = "segment", **opts) -> None:
     """The whole mapper on files, in process (tm_map_files; band: tm_map_files_band;
     band and gap_open: tm_map_files_band_affine, gap being the gap extend;
     band="auto": tm_map_files_band_exact, the unbanded results; extend_ends
     with a numeric band and the global type: tm_map_files_band_ends; zdrop
-    with extend_ends: tm_map_files_band_ends_zdrop)."""
+    with extend_ends: tm_map_files_band_ends_zdrop; zdrop_rule="stripe" with
+    zdrop: tm_map_files_band_ends_zdrop_rule)."""
     o = Options.make(**opts)
     zdrop = _check_zdrop(zdrop, extend_ends)
+    rule = _check_zdrop_rule(zdrop_rule, zdrop)
     if gap_open is not None and band is None:
         raise ValueError("gap_open needs a band: the mapper has no unbanded affine path")
     if extend_ends:
@@ -380,9 +399,12 @@ def map_files(reference: str, reads: str, out: str = "-", device: int = 0, band=
         if zdrop is None:
             _check(lib().tm_map_files_band_ends(reference.encode(), reads.encode(), C.byref(o), out.encode(), device,
                                                 0, int(band), go))
-        else:
+        elif rule == _align.TA_ZDROP_SEGMENT:
             _check(lib().tm_map_files_band_ends_zdrop(reference.encode(), reads.encode(), C.byref(o), out.encode(),
                                                       device, 0, int(band), go, zdrop))
+        else:
+            _check(lib().tm_map_files_band_ends_zdrop_rule(reference.encode(), reads.encode(), C.byref(o),
+                                                           out.encode(), device, 0, int(band), go, zdrop, rule))
         return
     if isinstance(band, str):
         if band != "auto":

@@ -770,6 +770,63 @@ int ta_align_batch_anchored_zdrop(ta_context* ctx, uint32_t n_pairs, const char*
                                   uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
                                   int32_t zdrop, uint32_t* swept_steps);
 
+/*
+ * ---- The row-stripe z-drop rule: a second, selectable definition of the drop.
+ * The rule above (TA_ZDROP_SEGMENT) follows the fill's sweep, whose segments at
+ * the end of a 1024-row pass and at the start of a pass with c0 > 1 hold only
+ * cells near one edge of the band: at w > 32 it can drop a LIVE end at a pass
+ * boundary.  The stripe rule is tied to rows.  Every stripe holds the cells
+ * through which any path crosses its rows, so a live end cannot drop, whatever
+ * the band and wherever a pass boundary falls: TA_ZDROP_STRIPE is the rule to
+ * use above w = 32.  (The default stays TA_ZDROP_SEGMENT: the existing entries
+ * keep their results, and the segment rule detects a dead end about one
+ * stripe's sweep sooner.)
+ * Cell values, band, boundaries, tie order, '-' bytes, walk, "1\0", degenerate
+ * pairs, the range rule and 0 <= Z <= INT32_MAX are as above; nothing is
+ * pruned.  The rule only decides which cells EXIST for the goal scan
+ * (tests/anchored_zdrop_stripe_ref.py restates it; the geometry is ta_layout.h
+ * band_stripe_*):
+ *   Stripe g is rows 16 g + 1 .. min(16 g + 16, n), g = 0 .. ceil(n / 16) - 1.
+ *   Every row has an in-band interior cell, so no stripe is empty.
+ *   Stripe best: S_g = the maximum of -1 and every H of the stripe's in-band
+ *   interior cells.
+ *   Scan.  Stripes in order, B = 0 at the start: if B >= Z and S_g < B - Z the
+ *   pair DROPS at stripe g: stripe g's rows still exist, every later row does
+ *   not; otherwise B = max(B, S_g).  B carries across pass boundaries.
+ *   Goal: (0, 0) with score 0 unless an existing cell has H > 0, else the first
+ *   strict row-major maximum over the existing cells.  (It never lies in the
+ *   dropping stripe: S_g < B - Z <= B.)
+ *   swept_steps.  The fill tests the rule after every 64th step of a pass and
+ *   after the pass's last step, on every stripe whose last cell has been
+ *   computed.  Stripe g lies in pass p = g div 64 as lane l = g mod 64; its last
+ *   cell is computed at step tau_done = min(m, i_last + hi) - c0(p) + l, i_last =
+ *   min(n, 16 g + 16).  A drop at g executes the whole passes before p plus
+ *   min(steps_p, 64 (tau_done div 64 + 1)) steps; without a drop the sum of
+ *   steps_p; 0 for a degenerate pair.  tau_done strictly increases with l, so
+ *   the finished stripes are a prefix and testing in batches gives the
+ *   sequential scan's answer.  Rows below the dropping stripe that the fill has
+ *   computed by then do not exist all the same.
+ * rule: TA_ZDROP_SEGMENT or TA_ZDROP_STRIPE, else TA_ERR_ARG (whatever zdrop).
+ * zdrop < 0 is off for either rule.  Planning is the segment rule's; _swept_steps,
+ * _ends, _annotate, _check and _pair_chunks work unchanged on a stripe plan;
+ * certification does not cover the mode.  `flags` as ta_anchored_plan_create.
+ */
+#define TA_ZDROP_SEGMENT 0
+#define TA_ZDROP_STRIPE 1
+int ta_anchored_plan_create_zdrop_rule(ta_context* ctx, uint32_t n_pairs, const uint32_t* query_len_host,
+                                       const uint32_t* target_len_host, const uint32_t* band_host, int match,
+                                       int mismatch, int gap_open, int gap_extend, int want_cigar,
+                                       uint64_t workspace_budget, uint32_t flags, int32_t zdrop, int rule,
+                                       ta_anchored_plan** out);
+int ta_align_batch_anchored_zdrop_rule(ta_context* ctx, uint32_t n_pairs, const char* query_bytes,
+                                       const uint64_t* query_off, const uint32_t* query_len,
+                                       const char* target_bytes, const uint64_t* target_off,
+                                       const uint32_t* target_len, const uint32_t* band, int match, int mismatch,
+                                       int gap_open, int gap_extend, int want_cigar, int32_t* score,
+                                       uint32_t* query_end, uint32_t* target_end, char* cigar_arena,
+                                       uint64_t cigar_arena_bytes, uint64_t* cigar_off, uint32_t* cigar_len,
+                                       int32_t zdrop, int rule, uint32_t* swept_steps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,6 +218,16 @@ int tm_map_batch_band_ends_zdrop(tm_context* ctx, const tm_index* idx, uint32_t 
                                  uint32_t* t_end, int32_t* score, char* cigar_arena, uint64_t cigar_arena_bytes,
                                  uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags, ta_pair_info* info,
                                  uint32_t band, const int* gap_open, int32_t zdrop);
+/* ... with the z-drop rule chosen (team_mapper_amd --zdrop Z --zdrop-rule segment|stripe): zdrop_rule is
+ * TA_ZDROP_SEGMENT (tm_map_batch_band_ends_zdrop exactly) or TA_ZDROP_STRIPE, the row-stripe rule of
+ * team_align_c.h, which does not clip a live end at a pass boundary and is the rule to use above band 32;
+ * any other value: TM_ERR_ARG.  Both end plans get the rule (ta_anchored_plan_create_zdrop_rule). */
+int tm_map_batch_band_ends_zdrop_rule(tm_context* ctx, const tm_index* idx, uint32_t n_reads, const char* bytes,
+                                      const uint64_t* off, const uint32_t* len, const tm_options* opt, uint8_t* mapped,
+                                      uint8_t* strand_fwd, uint32_t* q_begin, uint32_t* q_end, uint32_t* t_begin,
+                                      uint32_t* t_end, int32_t* score, char* cigar_arena, uint64_t cigar_arena_bytes,
+                                      uint64_t* cigar_off, uint32_t* cigar_len, uint32_t flags, ta_pair_info* info,
+                                      uint32_t band, const int* gap_open, int32_t zdrop, int zdrop_rule);
 
 /* Wall time (ms) of the last tm_map_batch on this context, per stage:
  * [0] read upload, [1] minimizers, [2] seed matching, [3] FindLIS chaining,
@@ -264,6 +274,10 @@ int tm_map_files_band_ends(const char* reference_path, const char* reads_path, c
 int tm_map_files_band_ends_zdrop(const char* reference_path, const char* reads_path, const tm_options* opt,
                                  const char* out_path, int device, uint32_t flags, uint32_t band,
                                  const int* gap_open, int32_t zdrop);
+/* ... through tm_map_batch_band_ends_zdrop_rule (team_mapper_amd ... --zdrop Z --zdrop-rule segment|stripe). */
+int tm_map_files_band_ends_zdrop_rule(const char* reference_path, const char* reads_path, const tm_options* opt,
+                                      const char* out_path, int device, uint32_t flags, uint32_t band,
+                                      const int* gap_open, int32_t zdrop, int zdrop_rule);
 
 #ifdef __cplusplus
 }
