@@ -105,12 +105,16 @@ def lib() -> C.CDLL:
                                     C.c_void_p, C.c_void_p]
     L.ta_plan_execute_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.ta_plan_execute_traceback.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ta_plan_execute_walk.argtypes = L.ta_plan_execute_traceback.argtypes
+    L.ta_plan_execute_format.argtypes = L.ta_plan_execute_traceback.argtypes
+    L.ta_plan_format_is_split.argtypes = [C.c_void_p, C.c_uint32]
     L.ta_pipeline_create.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]
     L.ta_pipeline_create_affine.argtypes = L.ta_pipeline_create.argtypes
     L.ta_pipeline_create_ex.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p)]
     L.ta_pipeline_create_affine_ex.argtypes = L.ta_pipeline_create_ex.argtypes
     L.ta_pipeline_walk_streams.argtypes = [C.c_void_p]
     L.ta_pipeline_walk_streams.restype = C.c_uint32
+    L.ta_pipeline_format_split.argtypes = [C.c_void_p]
     L.ta_pipeline_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u32p]
     L.ta_pipeline_destroy.argtypes = [C.c_void_p]
     L.ta_pipeline_destroy.restype = None
@@ -243,6 +247,7 @@ ABI_SYMBOLS = [
     "ta_plan_context", "ta_affine_plan_context", "ta_context_device",
     "ta_pipeline_create", "ta_pipeline_create_affine", "ta_pipeline_step", "ta_pipeline_destroy",
     "ta_pipeline_create_ex", "ta_pipeline_create_affine_ex", "ta_pipeline_walk_streams",
+    "ta_plan_execute_walk", "ta_plan_execute_format", "ta_plan_format_is_split", "ta_pipeline_format_split",
 ]
 # The banded extension's symbols (checked by tests/test_banded_ref.py).
 BANDED_ABI_SYMBOLS = [
@@ -1075,7 +1080,10 @@ class DevicePipeline:
     dependencies are the library's (ta_pipeline_* of team_align_c.h,
     csrc/ta_pipeline.cpp): each slot's fills run on a fill stream of the slot's
     own, so a fill also overlaps the tail of the fill before it; tracebacks on
-    a high-priority walk stream; and the caller's
+    a high-priority walk stream -- where a traceback is a walk kernel and a run
+    formatter (checkpoint and band walks, one chunk) only the walk, and the
+    formatter on the caller's stream beside the next walk (``format_split``);
+    and the caller's
     current stream waits for each step's traceback, so whatever the caller
     enqueues after step() on its stream (a compaction, a gather, the next
     upload into this step's input buffers) follows it; a slot's next fill also
@@ -1092,7 +1100,7 @@ class DevicePipeline:
 
     def __init__(self, device: int, batch, type, match, mismatch, gap, want_cigar=True, depth: int = 3,
                  workspace_budget: int = 0, gap_open=None, flags: int = 0, inputs=None, first=None,
-                 walk_streams=None):
+                 walk_streams=None, format_stream=None):
         """first: an existing DevicePlan (on its own Aligner) to use as slot 0;
         the other slots then start on its inputs.  depth: the slots (>= 2).
         At 2, fill k+2 waits for walk k, which ends only shortly before fill
@@ -1104,7 +1112,11 @@ class DevicePipeline:
         (1 .. depth; step k's traceback runs on stream k % walk_streams, so
         consecutive walks may overlap); None: the library's default, which
         depends on GPU_MAX_HW_QUEUES (ta_pipeline_create_ex in
-        team_align_c.h).  ``self.walk_streams`` is the count in use."""
+        team_align_c.h).  ``self.walk_streams`` is the count in use.
+        format_stream: None or 0, the library's default -- the run formatter
+        on the caller's stream where the plans allow it; 1 keeps it on the
+        walk stream behind its walk.  ``self.format_split`` is what is in use
+        (True: formatters on the caller's stream)."""
         import torch
 
         self.torch = torch
@@ -1125,7 +1137,8 @@ class DevicePipeline:
         handles = (C.c_void_p * len(self.plans))(*[p._h for p in self.plans])
         h = C.c_void_p()
         create = L.ta_pipeline_create_affine_ex if self.plans[0].affine else L.ta_pipeline_create_ex
-        opts = (C.c_uint32 * 2)(8, int(walk_streams or 0))  # ta_pipeline_options: size, walk_streams
+        # ta_pipeline_options: size, walk_streams, format_stream
+        opts = (C.c_uint32 * 3)(12, int(walk_streams or 0), int(format_stream or 0))
         r = create(handles, len(self.plans), opts, C.byref(h))
         if r != TA_OK:
             msg = L.ta_last_error(self.plans[0]._ctx).decode()
@@ -1138,6 +1151,7 @@ class DevicePipeline:
             raise DeviceError(f"{L.ta_status_string(r).decode()}: {msg}")
         self._h = h
         self.walk_streams = L.ta_pipeline_walk_streams(h)
+        self.format_split = bool(L.ta_pipeline_format_split(h))
 
     @property
     def chunks(self):
@@ -1146,7 +1160,8 @@ class DevicePipeline:
     def step(self, inputs=None, ready=None):
         """Enqueue one batch (ta_pipeline_step): its fill on the slot's fill
         stream, its traceback on the walk stream (the current stream waits for
-        it).  inputs: this batch's
+        it; with ``format_split`` the run formatter is enqueued on the current
+        stream itself).  inputs: this batch's
         (query bytes, query offsets, target bytes, target offsets) tensors in
         HBM, same shapes as planned; ready: an event the fill waits for first
         (None: the inputs are resident); ``ready`` without ``inputs`` is a

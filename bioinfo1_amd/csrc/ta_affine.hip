@@ -1009,7 +1009,7 @@ struct TA_PLAN_LOCAL ta_affine_plan : ta::AffineArrays {  // the opaque plan, as
     ta_context* ctx = nullptr;
     ta::AffinePlan h;
     void* own_block = nullptr;  // device arrays of a plan made by ta_affine_plan_create (one allocation)
-    static int exec_chunk(ta_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace);
+    static int exec_chunk(ta_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, ta::TraceParts trace);
     // (int32-only plans without pipelined passes poll nothing)
     uint32_t* err_word() const { return h.duals.empty() && h.single_tasks.empty() ? nullptr : d_err; }
     static const char* err_message(uint32_t) {
@@ -1042,7 +1042,7 @@ int affine_check_args(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, c
 
 }  // namespace
 
-int ta_affine_plan::exec_chunk(ta_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace) {
+int ta_affine_plan::exec_chunk(ta_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, ta::TraceParts trace) {
     ta_context* ctx = pl->ctx;
     const ta::AffinePlan& h = pl->h;
     if (int r = ta_host::grow(ctx, ctx->ws_ptrs, h.ws_ptr_entries * sizeof(uint2))) return r;
@@ -1121,7 +1121,7 @@ int ta_affine_plan::exec_chunk(ta_affine_plan* pl, const ta_device_io* io, hipSt
         TA_HIP(ctx, ta::launch_affine_fill(h.type, h.want_cigar, sa, s));
         roctxRangePop();
     }
-    if (trace && h.want_cigar) {
+    if ((trace & ta::kTraceWalk) && h.want_cigar) {  // (the walk writes the text: the whole traceback)
         roctxRangePushA("ta affine traceback");
         TA_HIP(ctx, ta::launch_affine_traceback(h.type, a, s));
         roctxRangePop();

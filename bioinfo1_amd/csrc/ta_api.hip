@@ -29,7 +29,9 @@ struct TA_PLAN_LOCAL ta_plan : ta::PlanArrays {  // device arrays: inside own_bl
     ta_context* ctx = nullptr;
     ta::Plan h;                 // host plan (ta_planner.h)
     void* own_block = nullptr;  // device arrays of a plan made by ta_plan_create (one allocation)
-    static int exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace);
+    // trace: the parts of the traceback to enqueue (ta::kTraceWalk | ta::kTraceFormat; 0: none)
+    static int exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, ta::TraceParts trace);
+    uint32_t code_layout() const { return h.blk ? (h.ck ? 2u : 1u) : 0u; }  // FillArgs / TraceArgs blk
     // (int32-only plans without pipelined passes have no kernel that reports)
     uint32_t* err_word() const { return h.flexes.empty() && h.duals.empty() && h.single_tasks.empty() ? nullptr : d_err; }
     static const char* err_message(uint32_t err) {
@@ -51,8 +53,10 @@ int check_args(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, const ui
 
 // Launches of one chunk: the fill kernels (int32 singles, equal-shape dual
 // couples, rebased flex couples, and the int32 fill of the couples the packed
-// kernels hand back), then the traceback kernel.
-int ta_plan::exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace) {
+// kernels hand back), then the traceback: its walk kernel and, for the walks
+// that leave runs (checkpoint and band walks), the run formatter -- either
+// part alone for ta_plan_execute_walk / _format.
+int ta_plan::exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, ta::TraceParts trace) {
     const ta::Plan& h = pl->h;
     const auto& ch = h.chunks[c];
     ta_context* ctx = pl->ctx;
@@ -98,7 +102,7 @@ int ta_plan::exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint
         a.slot_off = pl->d_slot_off;
         a.cigar_start = io->cigar_start;
         a.cigar_len = io->cigar_len;
-        a.blk = h.blk ? (h.ck ? 2u : 1u) : 0u;
+        a.blk = pl->code_layout();
         a.pflag = (h.blk && h.walk_group == 64) ? pl->d_pflag : nullptr;
         if (ch.scount) {  // launched first: it may run on the aux stream beside the packed fill
             ta::FillArgs a1 = a;
@@ -213,7 +217,7 @@ int ta_plan::exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint
         t.match = h.match;
         t.mismatch = h.mismatch;
         t.gap = h.gap;
-        t.blk = h.blk ? (h.ck ? 2u : 1u) : 0u;
+        t.blk = pl->code_layout();
         if (h.walk_group == 64) {
             // band walks (one lane per pair), then the pairs of the couples the dual
             // fill handed back ('-' bytes) in the one-pair walk: its list and count
@@ -222,9 +226,9 @@ int ta_plan::exec_chunk(ta_plan* pl, const ta_device_io* io, hipStream_t s, uint
             t.err = pl->d_err;
             t.fb_order = pl->d_fb + 2ull * ch.cbegin;
             t.fb_count = pl->d_fb + h.n_dual_pairs + c;
-            TA_HIP(ctx, ta::launch_traceback(h.type, t, s, 64));
+            TA_HIP(ctx, ta::launch_traceback(h.type, t, s, 64, trace));
         } else {
-            TA_HIP(ctx, ta::launch_traceback(h.type, t, s, h.walk_group));
+            TA_HIP(ctx, ta::launch_traceback(h.type, t, s, h.walk_group, trace));
         }
         roctxRangePop();
     }
@@ -358,6 +362,16 @@ int ta_plan_execute_fill(ta_plan* pl, const ta_device_io* io, void* stream, uint
 }
 int ta_plan_execute_traceback(ta_plan* pl, const ta_device_io* io, void* stream, uint32_t chunk) {
     return ta_host::plan_execute_chunk(pl, io, stream, chunk, false);
+}
+int ta_plan_execute_walk(ta_plan* pl, const ta_device_io* io, void* stream, uint32_t chunk) {
+    return ta_host::plan_execute_chunk(pl, io, stream, chunk, false, ta::kTraceWalk);
+}
+int ta_plan_execute_format(ta_plan* pl, const ta_device_io* io, void* stream, uint32_t chunk) {
+    return ta_host::plan_execute_chunk(pl, io, stream, chunk, false, ta::kTraceFormat);
+}
+int ta_plan_format_is_split(const ta_plan* pl, uint32_t chunk) {
+    if (!pl || chunk >= pl->h.chunks.size() || !pl->h.want_cigar || pl->h.fused) return 0;
+    return ta::traceback_has_formatter(pl->h.type, pl->code_layout(), pl->h.walk_group) ? 1 : 0;
 }
 int ta_plan_check(ta_plan* pl) { return ta_host::plan_check(pl); }
 int ta_plan_annotate(ta_plan* pl, const ta_device_io* io, const ta_annotate_io* out, void* stream) {

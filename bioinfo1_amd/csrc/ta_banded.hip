@@ -606,7 +606,7 @@ struct TA_PLAN_LOCAL ta_banded_plan : ta::BandArrays {  // the opaque plan, as t
     ta_context* ctx = nullptr;
     ta::BandPlan h;
     void* own_block = nullptr;  // device arrays of a plan made by ta_banded_plan_create (one allocation)
-    static int exec_chunk(ta_banded_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace);
+    static int exec_chunk(ta_banded_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, ta::TraceParts trace);
     uint32_t* err_word() const { return nullptr; }  // (no polls: one wave sweeps a pair's passes)
     static const char* err_message(uint32_t) { return ""; }
 };
@@ -627,7 +627,7 @@ int band_check_args(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen, con
 
 }  // namespace
 
-int ta_banded_plan::exec_chunk(ta_banded_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, bool trace) {
+int ta_banded_plan::exec_chunk(ta_banded_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill, ta::TraceParts trace) {
     ta_context* ctx = pl->ctx;
     const ta::BandPlan& h = pl->h;
     if (int r = ta_host::grow(ctx, ctx->ws_ptrs, h.ws_ptr_dwords * 4)) return r;
@@ -666,7 +666,7 @@ int ta_banded_plan::exec_chunk(ta_banded_plan* pl, const ta_device_io* io, hipSt
         TA_HIP(ctx, ta::launch_banded_fill(h.type, h.want_cigar, h.zdrop_rule, a, s));
         roctxRangePop();
     }
-    if (trace && h.want_cigar) {
+    if ((trace & ta::kTraceWalk) && h.want_cigar) {  // (the walk writes the text: the whole traceback)
         roctxRangePushA("ta banded traceback");
         TA_HIP(ctx, ta::launch_banded_traceback(h.type, a, s));
         roctxRangePop();

@@ -551,7 +551,7 @@ struct TA_PLAN_LOCAL ta_banded_affine_plan : ta::BandArrays {  // the opaque pla
     ta::BandAffinePlan h;
     void* own_block = nullptr;  // device arrays of a plan made by ta_banded_affine_plan_create (one allocation)
     static int exec_chunk(ta_banded_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c, bool fill,
-                          bool trace);
+                          ta::TraceParts trace);
     uint32_t* err_word() const { return nullptr; }  // (no polls: one wave sweeps a pair's passes)
     static const char* err_message(uint32_t) { return ""; }
 };
@@ -575,7 +575,7 @@ int band_aff_check_args(ta_context* ctx, uint32_t n_pairs, const uint32_t* qlen,
 }  // namespace
 
 int ta_banded_affine_plan::exec_chunk(ta_banded_affine_plan* pl, const ta_device_io* io, hipStream_t s, uint32_t c,
-                                      bool fill, bool trace) {
+                                      bool fill, ta::TraceParts trace) {
     ta_context* ctx = pl->ctx;
     const ta::BandAffinePlan& h = pl->h;
     if (int r = ta_host::grow(ctx, ctx->ws_ptrs, h.ws_ptr_entries * sizeof(uint2))) return r;
@@ -615,7 +615,7 @@ int ta_banded_affine_plan::exec_chunk(ta_banded_affine_plan* pl, const ta_device
         TA_HIP(ctx, ta::launch_banded_affine_fill(h.type, h.want_cigar, h.zdrop_rule, a, s));
         roctxRangePop();
     }
-    if (trace && h.want_cigar) {
+    if ((trace & ta::kTraceWalk) && h.want_cigar) {  // (the walk writes the text: the whole traceback)
         roctxRangePushA("ta banded affine traceback");
         TA_HIP(ctx, ta::launch_banded_affine_traceback(h.type, a, s));
         roctxRangePop();

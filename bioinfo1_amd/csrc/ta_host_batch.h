@@ -134,7 +134,7 @@ int host_batch(ta_context* ctx, PL& pl, uint32_t n_pairs, const char* qb, const 
     io.cigar_len = reinterpret_cast<uint32_t*>(dout + o_cl);
     io.cigar_start = reinterpret_cast<uint64_t*>(dout + o_cs);
     io.cigar_slots = reinterpret_cast<char*>(dout + o_sl);
-    if (int r = exec(&pl, &io, s, UINT32_MAX, true, true)) return r;
+    if (int r = exec(&pl, &io, s, UINT32_MAX, true, ta::kTraceAll)) return r;
     const bool whole = !want_cigar || slots <= kSmallSlots;
     const uint64_t down = whole ? O.bytes : o_sl;
     const uint32_t* d_err = pl.err_word();

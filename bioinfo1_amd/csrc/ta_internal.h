@@ -208,8 +208,14 @@ template <int MODE, bool CIGAR>
 hipError_t launch_fill_mode(bool wide, const FillArgs& a, hipStream_t s);
 // group: 32 = local walks of two pairs per wave (ta_walk2.h), 16 = lane walks
 // (ta_walk_lane.h), 64 = band walks (one lane per pair, ta_walk_band.h; blocked
-// layout), 0 = one pair per wave
-hipError_t launch_traceback(int mode, const TraceArgs& a, hipStream_t s, int group);
+// layout), 0 = one pair per wave.  Checkpoint walks (TraceArgs.blk == 2, any mode) and
+// band walks leave runs that format_runs_kernel turns into CIGAR text
+// (traceback_has_formatter); `parts` selects the walk, the formatter or both.  The
+// other walks write the text themselves: kTraceWalk is all of them, kTraceFormat
+// alone launches nothing.
+enum TraceParts : int { kTraceWalk = 1, kTraceFormat = 2, kTraceAll = 3 };
+bool traceback_has_formatter(int mode, uint32_t blk, int group);
+hipError_t launch_traceback(int mode, const TraceArgs& a, hipStream_t s, int group, int parts = kTraceAll);
 // Dual-pair packed int16 fill (ta_dual.hip): a.order holds 2 pair ids per wave.
 hipError_t launch_dual(int mode, bool cigar, const FillArgs& a, hipStream_t s);
 template <int MODE, bool CIGAR>

@@ -1070,22 +1070,28 @@ hipError_t launch_flex(int mode, bool cigar, const FillArgs& a, hipStream_t s) {
     }
 }
 
-hipError_t launch_traceback(int mode, const TraceArgs& a, hipStream_t s, int group) {
+bool traceback_has_formatter(int mode, uint32_t blk, int group) {
+    return group == 64 && (blk == 2 || mode == kLocal);  // checkpoint walks (any mode) and band walks
+}
+
+hipError_t launch_traceback(int mode, const TraceArgs& a, hipStream_t s, int group, int parts) {
     if (!a.count) return hipSuccess;
     const dim3 g = grid_for(a.count), b(kBlock);
+    if (traceback_has_formatter(mode, a.blk, group)) {
+        if (parts & kTraceWalk) {
+            if (a.blk == 2) {  // recomputing walks over checkpoints (ta_walk_ck.hip), any mode
+                const hipError_t e = launch_walk_ck(mode, a, s);
+                if (e != hipSuccess) return e;
+            } else {  // band walks (blocked layout), one lane per pair
+                hipLaunchKernelGGL(traceback_band_kernel, dim3((a.count + kWave - 1) / kWave), dim3(kWave), 0, s, a);
+            }
+        }
+        if (parts & kTraceFormat) hipLaunchKernelGGL(format_runs_kernel, g, b, 0, s, a);
+        return hipGetLastError();
+    }
+    if (!(parts & kTraceWalk)) return hipSuccess;  // no formatter kernel: the walk below is the whole traceback
     if (mode == kLocal && group == 32) {
         hipLaunchKernelGGL(traceback_group_kernel<32>, grid_for((a.count + 1) / 2), b, 0, s, a);
-        return hipGetLastError();
-    }
-    if (group == 64 && a.blk == 2) {  // recomputing walks over checkpoints (ta_walk_ck.hip), any mode
-        const hipError_t e = launch_walk_ck(mode, a, s);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(format_runs_kernel, g, b, 0, s, a);
-        return hipGetLastError();
-    }
-    if (mode == kLocal && group == 64) {  // band walks (blocked layout), one lane per pair
-        hipLaunchKernelGGL(traceback_band_kernel, dim3((a.count + kWave - 1) / kWave), dim3(kWave), 0, s, a);
-        hipLaunchKernelGGL(format_runs_kernel, g, b, 0, s, a);
         return hipGetLastError();
     }
     if (mode == kLocal && group == 16) {  // lane walks (TA_LW_G lanes per pair)

@@ -14,13 +14,30 @@
 // run alone on a mostly idle chip (they could not become resident while walk
 // k held registers), fill k+2's blocks take the free CUs.
 //
-// WALK STREAMS: ta_pipeline_create keeps one, so walks and their formatters run
-// back to back.  With walk_streams = w (ta_pipeline_create_ex) step k's
+// WALK STREAMS: ta_pipeline_create keeps one, so walks run back to back (with
+// their formatters between them in the combined order, below).  With
+// walk_streams = w (ta_pipeline_create_ex) step k's
 // traceback goes to walk stream k % w -- the step index, not the slot's, so
 // consecutive steps alternate whatever the depth -- and walk k+1 may start
 // beside walk k's tail and its formatter.  Nothing else changes: a walk still
 // follows its own fill through the slot's context, the caller's stream waits
 // for every step's walk in step order, and a fill for its slot's done event.
+//
+// THE RUN FORMATTER OFF THE WALK STREAM.  With one walk stream the step period
+// is that stream's chain: walk, formatter, the launch gap to the next walk.
+// Walk k+1 needs its own fill and the walk stream, nothing the formatter of
+// step k writes; only the caller's stream and the slot's next fill need that.
+// So where a slot's traceback is a walk kernel and a formatter kernel
+// (ta_plan_format_is_split: checkpoint and band walks) and the plan has one
+// chunk, a step enqueues the walk alone on the walk stream
+// (ta_plan_execute_walk), records walked[i] after it, lets the caller's stream
+// wait for that and enqueues the formatter on the CALLER'S stream
+// (ta_plan_execute_format): formatter k runs beside walk k+1, what the caller
+// enqueues afterwards follows it by stream order, and done[i], recorded on the
+// caller's stream at the next step, makes the slot's next fill follow it too.
+// No further stream, so no further hardware queue.  Plans of several chunks
+// (one workspace: a chunk's fill follows the formatter before it anyway),
+// affine slots and format_stream = 1 keep the combined traceback call.
 #ifndef __HIP_PLATFORM_AMD__
 #define __HIP_PLATFORM_AMD__ 1
 #endif
@@ -32,6 +49,7 @@
 #include <vector>
 
 #include "../../include/team_align_c.h"
+#define TA_PIPELINE_WEAK_REFS 1  // ta_plan_execute_walk / _format / _format_is_split may be absent (stand-in builds)
 #include "ta_pipeline_internal.h"
 
 namespace {
@@ -41,7 +59,12 @@ struct Ops {
     ta_context* (*context)(const void*);
     uint32_t (*chunks)(const void*);
     int (*fill)(void*, const ta_device_io*, void*, uint32_t);
-    int (*walk)(void*, const ta_device_io*, void*, uint32_t);
+    int (*walk)(void*, const ta_device_io*, void*, uint32_t);  // the whole traceback: walk and formatter
+    // the traceback in two executions, where the library has them and the plan's traceback is
+    // two kernels (split); null: the family has only the combined call
+    bool (*split)(const void*);
+    int (*walk_only)(void*, const ta_device_io*, void*, uint32_t);
+    int (*format)(void*, const ta_device_io*, void*, uint32_t);
 };
 
 const Ops kLinear = {
@@ -52,6 +75,18 @@ const Ops kLinear = {
     },
     [](void* p, const ta_device_io* io, void* s, uint32_t c) {
         return ta_plan_execute_traceback(static_cast<ta_plan*>(p), io, s, c);
+    },
+    // (weak references, ta_pipeline_internal.h: absent in a build against stand-ins that lack them)
+    [](const void* p) {
+        const ta_plan* pl = static_cast<const ta_plan*>(p);
+        return ta_plan_execute_walk && ta_plan_execute_format && ta_plan_format_is_split && ta_plan_chunks(pl) == 1 &&
+               ta_plan_format_is_split(pl, 0) != 0;
+    },
+    [](void* p, const ta_device_io* io, void* s, uint32_t c) {
+        return ta_plan_execute_walk(static_cast<ta_plan*>(p), io, s, c);
+    },
+    [](void* p, const ta_device_io* io, void* s, uint32_t c) {
+        return ta_plan_execute_format(static_cast<ta_plan*>(p), io, s, c);
     },
 };
 
@@ -64,6 +99,9 @@ const Ops kAffine = {
     [](void* p, const ta_device_io* io, void* s, uint32_t c) {
         return ta_affine_plan_execute_traceback(static_cast<ta_affine_plan*>(p), io, s, c);
     },
+    nullptr,
+    nullptr,
+    nullptr,
 };
 
 int fail(ta_context* ctx, int code, const std::string& msg) {
@@ -89,11 +127,13 @@ struct ta_pipeline {
     std::vector<hipStream_t> fill;  // one per slot
     std::vector<hipStream_t> walk;  // step k's traceback on walk[k % size]; high priority: hardware queues beside the fills'
     // done[s]: recorded on the caller's stream at the step after slot s's, so it covers
-    // slot s's traceback and what the caller queued after it; walked[s]: slot s's traceback;
+    // slot s's traceback (its formatter on the caller's stream included) and what the caller
+    // queued after it; walked[s]: slot s's traceback (split: its walk);
     // start: the caller's stream at the first step (a slot's first fill follows it)
     std::vector<hipEvent_t> done, walked;
     hipEvent_t start = nullptr;
     std::vector<bool> used;
+    bool split = false;  // every step: the walk on the walk stream, the formatter on the caller's
     uint64_t k = 0;
     int last = -1;
 };
@@ -135,11 +175,15 @@ int create(const Ops& ops, void* const* slots, uint32_t depth, const ta_pipeline
                 return fail(c0, TA_ERR_ARG, "ta_pipeline_create: two slots share a context (each needs its own workspace)");
     }
     // (fields beyond the caller's `size` read as 0; no options: ta_pipeline_create's one walk stream)
-    uint32_t w = 1;
+    uint32_t w = 1, format_stream = 0;
     if (opt) {
         const bool has = opt->size >= offsetof(ta_pipeline_options, walk_streams) + sizeof(opt->walk_streams);
         w = resolve_walk_streams(has ? opt->walk_streams : 0, depth);
+        if (opt->size >= offsetof(ta_pipeline_options, format_stream) + sizeof(opt->format_stream))
+            format_stream = opt->format_stream;
     }
+    if (format_stream > 1)
+        return fail(c0, TA_ERR_ARG, "ta_pipeline_create: format_stream must be 0 or 1 (" + std::to_string(format_stream) + ")");
     if (w > depth)
         return fail(c0, TA_ERR_ARG, "ta_pipeline_create: walk_streams exceeds depth (" + std::to_string(w) + " > " +
                                         std::to_string(depth) + ")");
@@ -153,6 +197,8 @@ int create(const Ops& ops, void* const* slots, uint32_t depth, const ta_pipeline
     p->done.assign(depth, nullptr);
     p->walked.assign(depth, nullptr);
     p->used.assign(depth, false);
+    p->split = format_stream == 0 && ops.split;
+    for (uint32_t a = 0; p->split && a < depth; ++a) p->split = ops.split(slots[a]);
     *out = p;
     return TA_OK;
 }
@@ -185,7 +231,7 @@ int ta_pipeline_create(ta_plan* const* slots, uint32_t depth, ta_pipeline** out)
 
 int ta_pipeline_create_ex(ta_plan* const* slots, uint32_t depth, const ta_pipeline_options* options,
                           ta_pipeline** out) {
-    const ta_pipeline_options defaults = {sizeof(ta_pipeline_options), 0};
+    const ta_pipeline_options defaults = {sizeof(ta_pipeline_options), 0, 0};
     return create(kLinear, reinterpret_cast<void* const*>(slots), depth, options ? options : &defaults, out);
 }
 
@@ -195,11 +241,12 @@ int ta_pipeline_create_affine(ta_affine_plan* const* slots, uint32_t depth, ta_p
 
 int ta_pipeline_create_affine_ex(ta_affine_plan* const* slots, uint32_t depth, const ta_pipeline_options* options,
                                  ta_pipeline** out) {
-    const ta_pipeline_options defaults = {sizeof(ta_pipeline_options), 0};
+    const ta_pipeline_options defaults = {sizeof(ta_pipeline_options), 0, 0};
     return create(kAffine, reinterpret_cast<void* const*>(slots), depth, options ? options : &defaults, out);
 }
 
 uint32_t ta_pipeline_walk_streams(const ta_pipeline* p) { return p ? (uint32_t)p->walk.size() : 0; }
+int ta_pipeline_format_split(const ta_pipeline* p) { return p && p->split ? 1 : 0; }
 
 int ta_pipeline_step(ta_pipeline* p, const ta_device_io* io, void* ready_event, void* caller_stream,
                      uint32_t* slot_out) {
@@ -230,13 +277,21 @@ int ta_pipeline_step(ta_pipeline* p, const ta_device_io* io, void* ready_event, 
     void* plan = p->slots[i];
     TP_HIP(ctx, hipStreamWaitEvent(p->fill[i], p->used[i] ? p->done[i] : p->start, 0));
     if (ready_event) TP_HIP(ctx, hipStreamWaitEvent(p->fill[i], static_cast<hipEvent_t>(ready_event), 0));
-    const uint32_t chunks = p->ops->chunks(plan);
-    for (uint32_t c = 0; c < chunks; ++c) {
-        if (int r = p->ops->fill(plan, io, p->fill[i], c)) return r;
-        if (int r = p->ops->walk(plan, io, walk, c)) return r;  // (after the fill: the slot's context orders them)
+    if (p->split) {  // (one chunk) the walk stream's chain is walk -> walk: the formatter runs beside the next walk
+        if (int r = p->ops->fill(plan, io, p->fill[i], 0)) return r;
+        if (int r = p->ops->walk_only(plan, io, walk, 0)) return r;  // (after the fill: the slot's context orders them)
+        TP_HIP(ctx, hipEventRecord(p->walked[i], walk));
+        TP_HIP(ctx, hipStreamWaitEvent(cur, p->walked[i], 0));
+        if (int r = p->ops->format(plan, io, cur, 0)) return r;
+    } else {
+        const uint32_t chunks = p->ops->chunks(plan);
+        for (uint32_t c = 0; c < chunks; ++c) {
+            if (int r = p->ops->fill(plan, io, p->fill[i], c)) return r;
+            if (int r = p->ops->walk(plan, io, walk, c)) return r;  // (after the fill: the slot's context orders them)
+        }
+        TP_HIP(ctx, hipEventRecord(p->walked[i], walk));
+        TP_HIP(ctx, hipStreamWaitEvent(cur, p->walked[i], 0));
     }
-    TP_HIP(ctx, hipEventRecord(p->walked[i], walk));
-    TP_HIP(ctx, hipStreamWaitEvent(cur, p->walked[i], 0));
     p->used[i] = true;
     p->last = (int)i;
     ++p->k;

@@ -7,7 +7,9 @@
 // PL is a family's opaque plan struct.  It derives from the family's device
 // arrays (ta_plan_block.h) and holds
 //     ta_context* ctx;  <host plan> h;  void* own_block;
-//     static int exec_chunk(PL*, const ta_device_io*, hipStream_t, uint32_t c, bool fill, bool trace);
+//     static int exec_chunk(PL*, const ta_device_io*, hipStream_t, uint32_t c, bool fill, ta::TraceParts trace);
+//         (trace: the parts of the traceback to enqueue, or kNoTrace.  A family whose walks write the
+//         CIGAR text themselves runs its traceback for kTraceWalk and nothing for kTraceFormat alone.)
 //     uint32_t* err_word() const;  // the device word this plan's kernels report errors in, or null
 //     static const char* err_message(uint32_t err);  // what a nonzero error word means
 // exec_chunk (which kernels a chunk launches, on which streams) is the
@@ -86,9 +88,12 @@ int check_io(PL* pl, const ta_device_io* io) {
     return TA_OK;
 }
 
-// chunk == UINT32_MAX: every chunk.  Called with ctx->mu held.
+constexpr ta::TraceParts kNoTrace = ta::TraceParts(0);  // an execution of the fill alone
+
+// chunk == UINT32_MAX: every chunk.  trace: the parts of the traceback to enqueue (an enum, so
+// that no caller's `true` arrives as the walk alone).  Called with ctx->mu held.
 template <class PL>
-int exec(PL* pl, const ta_device_io* io, hipStream_t s, uint32_t chunk, bool fill, bool trace) {
+int exec(PL* pl, const ta_device_io* io, hipStream_t s, uint32_t chunk, bool fill, ta::TraceParts trace) {
     ta_context* ctx = pl->ctx;
     TA_HIP(ctx, hipSetDevice(ctx->device));
     if (int r = stream_enter(ctx, s)) return r;
@@ -103,17 +108,19 @@ template <class PL>
 int plan_execute(PL* pl, const ta_device_io* io, void* stream) {
     if (int r = check_io(pl, io)) return r;
     std::lock_guard<std::mutex> lock(pl->ctx->mu);
-    return exec(pl, io, (hipStream_t)stream, UINT32_MAX, true, true);
+    return exec(pl, io, (hipStream_t)stream, UINT32_MAX, true, ta::kTraceAll);
 }
 
-// One chunk's fill (fill) or traceback (!fill).  A chunk beyond the last is an
-// error, except on a plan of no pairs (which has no chunk to run).
+// One chunk's fill (fill) or traceback (!fill; parts: all of it, or its walk or
+// its run formatter alone).  A chunk beyond the last is an error, except on a
+// plan of no pairs (which has no chunk to run).
 template <class PL>
-int plan_execute_chunk(PL* pl, const ta_device_io* io, void* stream, uint32_t chunk, bool fill) {
+int plan_execute_chunk(PL* pl, const ta_device_io* io, void* stream, uint32_t chunk, bool fill,
+                       ta::TraceParts parts = ta::kTraceAll) {
     if (int r = check_io(pl, io)) return r;
     if (chunk >= pl->h.chunks.size()) return pl->h.n_pairs ? TA_ERR_ARG : TA_OK;
     std::lock_guard<std::mutex> lock(pl->ctx->mu);
-    return exec(pl, io, (hipStream_t)stream, chunk, fill, !fill);
+    return exec(pl, io, (hipStream_t)stream, chunk, fill, fill ? kNoTrace : parts);
 }
 
 template <class PL>

@@ -239,6 +239,22 @@ int ta_plan_check(ta_plan* plan);
 int ta_plan_execute_fill(ta_plan* plan, const ta_device_io* io, void* hip_stream, uint32_t chunk);
 int ta_plan_execute_traceback(ta_plan* plan, const ta_device_io* io, void* hip_stream, uint32_t chunk);
 
+/* The traceback in two executions, for a caller that wants the two on
+ * different streams (ta_pipeline_step below).  The traceback of checkpoint
+ * plans and of band-walk plans is a walk kernel, which leaves each pair's runs
+ * in the context's workspace, and a run formatter, which writes the CIGAR
+ * text: ta_plan_format_is_split returns 1 for such a chunk (0 otherwise, and
+ * for a chunk beyond the last).  There _walk enqueues the walk alone and
+ * _format the formatter alone; _format belongs after _walk and before the
+ * context's next fill, which the context's own ordering gives on any streams
+ * (an execution on another stream than the previous one waits for it first).
+ * For every other plan _walk is ta_plan_execute_traceback and _format
+ * enqueues nothing.  Arguments, errors and the bytes written are those of
+ * ta_plan_execute_traceback, which stays walk and formatter on one stream. */
+int ta_plan_execute_walk(ta_plan* plan, const ta_device_io* io, void* hip_stream, uint32_t chunk);
+int ta_plan_execute_format(ta_plan* plan, const ta_device_io* io, void* hip_stream, uint32_t chunk);
+int ta_plan_format_is_split(const ta_plan* plan, uint32_t chunk);
+
 /* The context a plan was created on, and a context's device. */
 ta_context* ta_plan_context(const ta_plan* plan);
 int ta_context_device(const ta_context* ctx);
@@ -265,6 +281,13 @@ int ta_context_device(const ta_context* ctx);
  *   - on `caller_stream`: a wait for that traceback, so what the caller
  *     enqueues there after the call sees this step's results, and may
  *     overwrite its inputs.
+ * Where every slot is a linear plan of one chunk whose traceback is split
+ * (ta_plan_format_is_split) the walk stream gets the walk alone and
+ * `caller_stream`, after its wait for the walk, the run formatter
+ * (ta_plan_execute_format): the formatter of step k then runs beside the walk
+ * of step k+1 instead of between the two, the caller's later work follows it
+ * by stream order and the slot's next fill follows that (format_stream below;
+ * ta_pipeline_format_split tells).  Results are the same bytes either way.
  * No fill waits for another slot's fill.  Errors (TA_ERR_ARG for a null
  * argument, TA_ERR_DEVICE) leave their message in ta_last_error of the slot's
  * context; argument errors enqueue nothing.  One thread at a time per pipeline.
@@ -300,6 +323,14 @@ void ta_pipeline_destroy(ta_pipeline* pipe);
  * environment.  The default is 1: on an MI355X two streams measured not
  * steadily faster than one for 10,000 pairs of 1 kb and three slower (DESIGN
  * 3.12), so the rule only matters to a build that defines another default.
+ *
+ * format_stream: 0, the default, puts the run formatter on the caller's stream
+ * where the slots allow it (above; no further stream or hardware queue); 1
+ * keeps it on the walk stream behind its walk, the order of
+ * ta_plan_execute_traceback (for comparisons, and as a way back); anything
+ * else is TA_ERR_ARG, the message names format_stream.  ta_pipeline_create /
+ * _create_affine take the default.  ta_pipeline_format_split returns 1 when
+ * the pipeline's steps enqueue walk and formatter apart, else 0.
  */
 #ifndef TA_PIPELINE_WALK_STREAMS_DEFAULT
 #define TA_PIPELINE_WALK_STREAMS_DEFAULT 1u
@@ -307,10 +338,12 @@ void ta_pipeline_destroy(ta_pipeline* pipe);
 typedef struct ta_pipeline_options {
     uint32_t size;         /* sizeof(ta_pipeline_options) */
     uint32_t walk_streams; /* 0: the default (above) */
+    uint32_t format_stream; /* 0: the default (above); 1: the formatter stays on the walk stream */
 } ta_pipeline_options;
 int ta_pipeline_create_ex(ta_plan* const* slots, uint32_t depth, const ta_pipeline_options* options,
                           ta_pipeline** out);
 uint32_t ta_pipeline_walk_streams(const ta_pipeline* pipe);
+int ta_pipeline_format_split(const ta_pipeline* pipe);
 
 /* Pack n_pairs CIGARs from their slots (device: cigar_slots, cigar_start,
  * cigar_len as written by an execution) back to back into dst (device):
